@@ -22,6 +22,10 @@ replicas` instead runs N independent schedulers (own cluster, own pod stream, no
 The CPU baseline is the parity oracle (oracle/, a C++ restatement of the reference) timed on a
 bounded sample of the same pod stream from the same initial state: its Filter/Score loops over
 nodes on 16 host threads (the reference's default parallelism), and on one thread beside it.
+
+A plain run sets up, warms up, times the steps and prints the result line.  `--full` adds what the
+headline figure does not need: the CPU baselines, the parity check of the timed stream against the
+oracle and the 100k-node C5 sub-record.  `--dump-outputs DIR` writes the last timed step's results.
 """
 import argparse
 import json
@@ -75,6 +79,14 @@ def parse():
                     help="steps (of --batch pods) of the C5 sub-record: 50 x 1000 = BASELINE configs[4]'s 50000 pods")
     ap.add_argument("--traffic", default=None,
                     help="PMC-derived HBM bytes per k_filter_score launch (from a separate rocprofv3 --pmc run)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run what the headline figure does not need: the oracle CPU "
+                         "baselines, the parity check of the timed stream against the oracle, and (default N=1 "
+                         "SchedulingBasic) the 100k-node C5 sub-record; --no-cpu-baseline / --no-verify / --no-sub "
+                         "leave single parts out.  Without it the line carries null for them")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step returned to its caller (the ksg_result array of its "
+                         "--batch pods, one column per file) as DIR/<name>.npy, float64")
     return ap.parse_args()
 
 
@@ -218,12 +230,25 @@ def cpu_baseline(nodes, init, pods, budget_s, threads=1, pct=100, objects=(), ex
     return done / dt, done, dt, results
 
 
+def dump_outputs(path, rs):
+    """The ksg_result array a timed step filled (what ksg_schedule_batch's caller receives: int32 status,
+    node_index, evaluated_nodes, feasible_nodes, int64 total_score per pod), one float64 .npy per field
+    (every value is an integer far below 2^53, so float64 holds it exactly)."""
+    rec = np.frombuffer(rs, dtype=np.dtype([("status", "<i4"), ("node_index", "<i4"), ("evaluated_nodes", "<i4"),
+                                            ("feasible_nodes", "<i4"), ("total_score", "<i8")]))
+    assert rec.shape == (len(rs),)
+    os.makedirs(path, exist_ok=True)
+    for name in rec.dtype.names:
+        np.save(os.path.join(path, name + ".npy"), rec[name].astype(np.float64))
+
+
 def sub_record(a):
     """The metric's 100k-node size (BASELINE configs[4], C5: the mixed 100k-node cluster on one GPU) measured
     by a child bench.py after this one's scheduler is gone: its pods/s, roofline, CPU baseline and parity."""
     import subprocess
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "c5", "--steps", str(a.sub_steps),
-           "--warmup", "1", "--batch", str(a.batch), "--cpu-seconds", str(min(a.cpu_seconds, 6.0)), "--no-sub"]
+           "--warmup", "1", "--batch", str(a.batch), "--cpu-seconds", str(min(a.cpu_seconds, 6.0)), "--no-sub",
+           "--full"]
     if a.no_cpu_baseline:
         cmd.append("--no-cpu-baseline")
     try:
@@ -356,6 +381,8 @@ def main():
     dt = time.perf_counter() - t0
     LOOP_PODS.extend(kstats)
     write_loop_pods()
+    if a.dump_outputs and rank == 0 and a.steps > 0:
+        dump_outputs(a.dump_outputs, arrays[-1][1])
     for _, rs in arrays:  # ksg_result: int32 status first, 24-byte records
         placed += int((np.frombuffer(rs, dtype=np.int32).reshape(len(rs), -1)[:, 0] == 0).sum())
     if dist is not None:
@@ -390,7 +417,7 @@ def main():
     if rank == 0:
         cpu = None
         warm = pods[:n_warm] if (a.pct != 100 or a.workload in PROFILES) else ()
-        if not a.no_cpu_baseline and world == 1:
+        if a.full and not a.no_cpu_baseline and world == 1:
             # the reference's default parallelism (16 goroutines over nodes), then one thread
             v, done, cdt, ores = cpu_baseline(nodes, init, pods[n_warm:], a.cpu_seconds, threads=a.cpu_threads,
                                               pct=a.pct, objects=objects, profile=PROFILES.get(a.workload), warm=warm)
@@ -478,7 +505,7 @@ def main():
         }
     s.close()
     if rank == 0:
-        if world == 1 and a.workload == "c2" and not a.no_sub and not sharded:
+        if a.full and world == 1 and a.workload == "c2" and not a.no_sub and not sharded:
             out["c5_100k"] = sub_record(a)
         print(json.dumps(out), flush=True)
     if dist is not None:
