@@ -135,6 +135,7 @@ typedef struct ksg_eval_out {
  *    "nodeAffinity": {"addedAffinity": <v1.NodeAffinity>},
  *    "podTopologySpread": {"defaultingType": "System" | "List",     (PodTopologySpreadArgs)
  *                          "defaultConstraints": [<v1.TopologySpreadConstraint without labelSelector>]},
+ *    "nominatedPods": "Refuse" | "Evaluate",               (other pods' nominations, see ksg_add_nominated_pod)
  *    "device": 0, "distributed": {"worldSize": 1, "rank": 0, "ncclId": "<hex>"}}
  * Absent keys take the upstream defaults.  Returns NULL on failure (ksg_create_error()). */
 ksg_ctx *ksg_create(const char *config_json, size_t len);
@@ -195,9 +196,22 @@ int ksg_forget(ksg_ctx *ctx, int32_t handle);
  * uid is forgotten).  ksg_delete_nominated_pod: DeleteNominatedPodIfExists (also done by every assume of the uid
  * through this context, schedule_one.go:1131-1134).  A pod's own nomination is evaluateNominatedNode (the pod
  * tries that node alone first).  OTHER pods' nominations change a pod's Filter: RunFilterPluginsWithNominatedPods
- * (framework.go:1211-1294) adds every pod of equal or higher priority nominated to a node before filtering it,
- * which this library does not run -- ksg_schedule_one / ksg_schedule_batch / ksg_preempt return KSG_ENOTSUP,
- * scheduling nothing, when a pod of the call has such a nomination on a snapshot node besides its own. */
+ * (framework.go:1211-1294) filters a node with every pod of equal or higher priority nominated to it added
+ * (NodeInfo.AddPodInfo: Requested, the pod count, scalar resources, host ports), and, if that passes, once more as
+ * the node is.  The ksg_create key "nominatedPods" selects what a call does when a pod of it has such a nomination
+ * on a snapshot node besides its own:
+ *   "Refuse" (default)  ksg_schedule_one / ksg_schedule_batch / ksg_preempt return KSG_ENOTSUP, scheduling nothing.
+ *   "Evaluate"          the device filters the node with those pods added and scores it as it is -- the full pass,
+ *                       the pod's own nominated node tried alone, the sampled pass and DefaultPreemption's dry
+ *                       run alike.  The nominator then keeps what AddPodInfo adds for each nominated pod.  Exact
+ *                       whenever NodeResourcesFit and NodePorts are the only filters that read the added pods;
+ *                       the call is still refused (KSG_ENOTSUP, nothing scheduled, the message names the pod and
+ *                       the condition) when a pod of it that would see such pods (a) has a DoNotSchedule
+ *                       topology spread constraint, its own or a profile default, (b) has a required pod
+ *                       affinity or anti-affinity term, or (c) would see a nominated pod that has a required
+ *                       anti-affinity term.  A batch is judged against the nominator as the call found it; inside
+ *                       it pod i sees the nominator as pods 0..i-1 left it.
+ * Any other value fails ksg_create (an invalid argument), and so does "Evaluate" on a node-sharded context. */
 int ksg_add_nominated_pod(ksg_ctx *ctx, const char *pod_json, size_t len);
 int ksg_delete_nominated_pod(ksg_ctx *ctx, const char *uid);
 

@@ -253,8 +253,29 @@ struct PodDesc {
   int64_t ob_now;                      // time.Now() of this cycle, ns (maxBatchAge, batch.go:57,208)
   // ---- evaluateNominatedNode (DF_NOMINATED)
   int32_t nominated_node;              // snapshot index of status.nominatedNodeName
-  int32_t nom_pad;
+  // ---- other pods' nominations (config nominatedPods "Evaluate", MirrorView::nom)
+  int32_t nom_self;                    // this pod's own record in the nominee table (never in its G), -1: none
+  int32_t nom_prio;                    // corev1helpers.PodPriority: G(p, n) is node n's records of priority >= this
+  int32_t nom_pad;                     // (both 0 / -1 while no nominee table is staged: programs compare as before)
 };
+
+// ---- the nominee table (RunFilterPluginsWithNominatedPods) ------------------------------
+// What NodeInfo.AddPodInfo adds to a node for every pod the nominator holds for it, staged by the host whenever
+// the nominator changed (Engine::nom_sync) and read-only on the device: one buffer, NomHdr, then head[n + 1]
+// (node i's records are [head[i], head[i + 1]), sorted by priority descending, so G(p, i) is a prefix of them
+// minus the pod's own record), the records, their host-port ids and their scalar resources.
+struct NomHdr {
+  int32_t n_rec;
+  int32_t rec_off, port_off, sc_off;  // byte offsets of NomRec[], uint32_t port ids[], ScalarReq[]
+};
+struct NomRec {
+  int64_t cpu, mem, eph;       // PodInfo.CalculateResource (Requested)
+  int32_t prio;
+  int32_t port_lo, port_cnt;   // its host-port ids in the port pool
+  int32_t sc_lo, sc_cnt;       // its scalar resources in the ScalarReq pool (mirror columns)
+  int32_t pad;
+};
+constexpr uint32_t NF_NOMINEES = 1u << 31;  // NodeCore::flags (not the mirror's column): the node has nominee records
 
 // ---- DefaultPreemption: SelectVictimsOnNode per node, one thread each ----------
 // The host lays out, per snapshot node, the pods isPreemptionAllowed admits (lower priority than the
@@ -457,6 +478,9 @@ struct MirrorView {
   int32_t port_slots;             // `ports` row stride: >= every node's host ports + what a batch can assume
   int32_t scalar_cols;            // scalar resource columns (>= the interned extended resources)
   int32_t pad_;
+  // the nominee table (NomHdr ...) the filters overlay on the node columns, never written by a kernel;
+  // nullptr: nothing is nominated to a snapshot node (or config nominatedPods "Refuse"): no lookup anywhere
+  const uint8_t* nom;
 };
 
 // Everything a per-pod kernel launch needs besides the mirror.

@@ -33,6 +33,12 @@ struct NodeCore {
   int32_t apods, npods;
   uint32_t flags, tlo, thi, ilo, ihi;  // taint and image CSR ranges
 };
+__device__ __forceinline__ const int32_t* nom_head(const uint8_t* tab) {
+  return reinterpret_cast<const int32_t*>(tab + sizeof(NomHdr));
+}
+// NOM: the instance looks at the nominee table (k_sched_loop's instances for launches with nothing nominated are
+// compiled without: the hot loop's code is then what it was before the table existed)
+template <bool NOM = true>
 __device__ __forceinline__ NodeCore load_core(const MirrorView& m, int i) {
   NodeCore c;
   c.acpu = m.alloc_cpu[i];
@@ -46,6 +52,12 @@ __device__ __forceinline__ NodeCore load_core(const MirrorView& m, int i) {
   c.apods = m.alloc_pods[i];
   c.npods = m.num_pods[i];
   c.flags = m.flags[i];
+  if constexpr (NOM) {
+    if (m.nom != nullptr) {  // (uniform: no lookup while nothing is nominated)
+      const int32_t* head = nom_head(m.nom);
+      c.flags |= head[i + 1] > head[i] ? NF_NOMINEES : 0u;
+    }
+  }
   c.tlo = m.taint_off[i];
   c.thi = m.taint_off[i + 1];
   c.ilo = m.img_off[i];
@@ -208,6 +220,107 @@ __shared__ unsigned long long s_diag[24];  // stamps land in LDS (a global store
   } while (0)
 #endif
 
+// ---- other pods' nominations (RunFilterPluginsWithNominatedPods, framework.go:1211-1294) ------
+// G(p, i): the pods nominated to node i of priority >= the pod's, but for the pod itself (addGENominatedPods).  What
+// NodeInfo.AddPodInfo adds for them: Requested, the pod count, host ports (as a conflict with the pod's own), and
+// -- nom_scalar -- scalar resources.  Only nodes whose core carries NF_NOMINEES get here (m.nom != nullptr).
+struct NomG {
+  int64_t cpu, mem, eph;
+  int32_t pods;
+  int32_t lo, hi;  // the record range the priority admits (the pod's own record may lie inside)
+  bool port;       // one of their host ports conflicts with the pod's (NodePorts active)
+};
+__device__ __forceinline__ NomG nom_gather(const MirrorView& m, const uint8_t* base, const PodDesc& d, int i) {
+  const uint8_t* tab = m.nom;
+  const NomHdr& h = *reinterpret_cast<const NomHdr*>(tab);
+  const int32_t* head = nom_head(tab);
+  const NomRec* rec = reinterpret_cast<const NomRec*>(tab + h.rec_off);
+  const uint32_t* pp = reinterpret_cast<const uint32_t*>(tab + h.port_off);
+  const int lo = head[i], end = head[i + 1];
+  NomG g{0, 0, 0, 0, lo, lo, false};
+  const bool ports_on = ((d.filter_mask >> P_PORTS) & 1u) != 0;
+  for (int q = lo; q < end; ++q) {
+    const NomRec r = rec[q];
+    if (r.prio < d.nom_prio) break;  // sorted by priority descending
+    g.hi = q + 1;
+    if (q == d.nom_self) continue;
+    g.cpu += r.cpu;
+    g.mem += r.mem;
+    g.eph += r.eph;
+    g.pods += 1;
+    for (int k = 0; ports_on && k < r.port_cnt; ++k)
+      g.port |= bit(base, d.port_conflict_off, pp[r.port_lo + k], d.n_port_words);
+  }
+  return g;
+}
+// G's Requested of scalar column `slot`
+__device__ __forceinline__ int64_t nom_scalar(const MirrorView& m, const PodDesc& d, const NomG& g, int32_t slot) {
+  const uint8_t* tab = m.nom;
+  const NomHdr& h = *reinterpret_cast<const NomHdr*>(tab);
+  const NomRec* rec = reinterpret_cast<const NomRec*>(tab + h.rec_off);
+  const ScalarReq* sc = reinterpret_cast<const ScalarReq*>(tab + h.sc_off);
+  int64_t sum = 0;
+  for (int q = g.lo; q < g.hi; ++q) {
+    if (q == d.nom_self) continue;
+    for (int k = 0; k < rec[q].sc_cnt; ++k) sum += sc[rec[q].sc_lo + k].slot == slot ? sc[rec[q].sc_lo + k].qty : 0;
+  }
+  return sum;
+}
+// The filter-side core: node i's core with G added.  Scores never read it (PreScore / Score see no nominated pod).
+__device__ __forceinline__ NodeCore nom_core(const NodeCore& nc, const NomG& g) {
+  NodeCore c = nc;
+  c.rcpu += g.cpu;
+  c.rmem += g.mem;
+  c.reph += g.eph;
+  c.npods += g.pods;
+  return c;
+}
+// Node i's Filter status with G added, from its status st0 without: the first failing plugin in the
+// RunFilterPlugins order.  Of the filters only NodePorts and NodeResourcesFit read what G adds (the host refuses
+// the pairs in which PodTopologySpread or InterPodAffinity would), both monotone in the pods added: a status from
+// a plugin before them stands, a NodePorts failure stands, and a success or a later plugin's failure gives way to
+// NodePorts', then NodeResourcesFit's, with G.  (Pass 2 of the reference, without G, then succeeds whenever this
+// does, so this status is the node's.)
+__device__ __forceinline__ uint32_t nom_status(const MirrorView& m, const NodeCore& nc, const uint8_t* base,
+                                               const PodDesc& d, int i, uint32_t st0) {
+  const uint32_t p0 = status_plugin(st0);
+  if (st0 != 0 && (p0 < (uint32_t)P_FIT || p0 > (uint32_t)P_IPA)) return st0;
+  const NomG g = nom_gather(m, base, d, i);
+  if (g.pods == 0) return st0;
+  if (g.port) return pack_status(C_UNSCHED, P_PORTS, KSG_R_NODE_PORTS);
+  if ((d.filter_mask >> P_FIT) & 1u) {  // fitsRequest (fit.go:593-734) on the filter-side core
+    const NodeCore fc = nom_core(nc, g);
+    uint32_t reasons = 0;
+    bool unresolvable = false;
+    if ((int64_t)fc.npods + 1 > (int64_t)fc.apods) reasons |= KSG_R_TOO_MANY_PODS;
+    if (d.fit_any) {
+      if (d.req_cpu > 0 && d.req_cpu > fc.acpu - fc.rcpu) {
+        reasons |= KSG_R_INSUFFICIENT_CPU;
+        unresolvable |= d.req_cpu > fc.acpu;
+      }
+      if (d.req_mem > 0 && d.req_mem > fc.amem - fc.rmem) {
+        reasons |= KSG_R_INSUFFICIENT_MEMORY;
+        unresolvable |= d.req_mem > fc.amem;
+      }
+      if (d.req_eph > 0 && d.req_eph > fc.aeph - fc.reph) {
+        reasons |= KSG_R_INSUFFICIENT_EPHEMERAL;
+        unresolvable |= d.req_eph > fc.aeph;
+      }
+      const ScalarReq* sr = at<ScalarReq>(base, d.scalar_off);
+      for (int k = 0; k < d.n_scalar; ++k) {
+        const size_t c = (size_t)sr[k].slot * (size_t)m.cap + (size_t)i;
+        const int64_t a = m.scalar_alloc[c];
+        if (sr[k].qty > a - (m.scalar_req[c] + nom_scalar(m, d, g, sr[k].slot))) {
+          reasons |= KSG_R_INSUFFICIENT_SCALAR;
+          unresolvable |= sr[k].qty > a;
+        }
+      }
+    }
+    if (reasons) return pack_status(unresolvable ? C_UU : C_UNSCHED, P_FIT, reasons);
+  }
+  return st0;
+}
+
 // ---- filters ------------------------------------------------------------------------------------
 // Where PodTopologySpread / InterPodAffinity read the pod's per-domain counts.  The launch path:
 // k_aggregate's arena in HBM and its PodStats reductions.  k_agg_loop: AggTopo (LDS).
@@ -229,8 +342,20 @@ __device__ __forceinline__ uint32_t topo_filters(const MirrorView& m, const uint
 // RunFilterPlugins order wins.  *raw_taint gets the PreferNoSchedule count while the taint
 // list is in registers.  ls: node i's slot in the caller's topology view (k_agg_loop).
 template <typename Topo>
+__device__ uint32_t run_filters_node(const MirrorView& m, const NodeCore& nc, const uint8_t* base, const PodDesc& d, int i,
+                                     int64_t* raw_taint, const Topo& tp, int ls);
+// ... with the pods nominated to node i added (nom_status)
+template <bool NOM = true, typename Topo>
 __device__ uint32_t run_filters(const MirrorView& m, const NodeCore& nc, const uint8_t* base, const PodDesc& d, int i,
                                 int64_t* raw_taint, const Topo& tp, int ls) {
+  uint32_t st = run_filters_node(m, nc, base, d, i, raw_taint, tp, ls);
+  if constexpr (NOM)
+    if (m.nom != nullptr && (nc.flags & NF_NOMINEES)) st = nom_status(m, nc, base, d, i, st);
+  return st;
+}
+template <typename Topo>
+__device__ uint32_t run_filters_node(const MirrorView& m, const NodeCore& nc, const uint8_t* base, const PodDesc& d, int i,
+                                     int64_t* raw_taint, const Topo& tp, int ls) {
   const uint32_t fm = d.filter_mask;
   // NodeUnschedulable (node_unschedulable.go:125-143)
   if ((fm >> P_UNSCHED) & 1u)
@@ -408,7 +533,7 @@ struct NodeEval {
 // 1378-1402).  kStore: write the node's status word (evaluation output), the weighted sum of the
 // non-normalising scores and the raw scores the normalising plugins need to the batch scratch
 // (the launch path's k_select reads them back; the persistent loop keeps them in registers).
-template <bool kStore>
+template <bool kStore, bool NOM = true>
 __device__ __forceinline__ NodeEval eval_node(const MirrorView& m, const BatchView& b, const uint8_t* base, const PodDesc& d, int pod,
                               int i, bool valid) {
   const bool eval = (d.flags & DF_EVAL_OUT) != 0;
@@ -417,7 +542,7 @@ __device__ __forceinline__ NodeEval eval_node(const MirrorView& m, const BatchVi
   int64_t raw_taint = 0;
   NodeCore nc{};
   DIAG_STAMP(0);
-  if (valid) nc = load_core(m, i);
+  if (valid) nc = load_core<NOM>(m, i);
   DIAG_STAMP(1);
   if (valid) {
     if (d.flags & DF_PREFILTER_REJECT) {
@@ -434,7 +559,7 @@ __device__ __forceinline__ NodeEval eval_node(const MirrorView& m, const BatchVi
       st = in ? 0u : pack_status(C_UU, 15u, KSG_R_PREFILTER);
     }
     if (st == 0) {
-      uint32_t f = run_filters(m, nc, base, d, i, &raw_taint, ArenaTopo{b.stats + pod, b.arena}, 0);
+      uint32_t f = run_filters<NOM>(m, nc, base, d, i, &raw_taint, ArenaTopo{b.stats + pod, b.arena}, 0);
       if (d.flags & DF_ALL_FEASIBLE)  // plugin-eval mode: the caller's node list is the feasible list
         f = ((d.flags & DF_NODE_LIST) && !bit(base, d.node_list_off, (uint32_t)i, (m.n + 31) / 32))
                 ? pack_status(C_UU, 15u, 0u)
@@ -598,6 +723,7 @@ __device__ __forceinline__ int64_t bal2(int64_t rc, int64_t ac, int64_t rm, int6
 // bal_wo: bal2 of the node without the pod (pod-independent: the loop keeps it per node)
 // bal_with: bal2 of the node with the pod, when the caller already has it (else kNoBal)
 constexpr int64_t kNoBal = INT64_MIN;
+template <bool NOM = true>
 __device__ __forceinline__ NodeEval eval_core_fast(const MirrorView& m, const NodeCore& nc, int64_t bal_wo,
                                                    const PodFast& pf, const uint8_t* base, const PodDesc& d, int i,
                                                    int64_t bal_with = kNoBal) {
@@ -650,6 +776,8 @@ __device__ __forceinline__ NodeEval eval_core_fast(const MirrorView& m, const No
       st = pack_status(unres ? C_UU : C_UNSCHED, P_FIT, reasons);
     }
   }
+  if constexpr (NOM)
+    if (m.nom != nullptr && (nc.flags & NF_NOMINEES)) st = nom_status(m, nc, base, d, i, st);
   r.st = st;
   DIAG_STAMP(11);
   if (st != 0) return r;
@@ -1178,8 +1306,8 @@ __global__ void k_ob_hint(MirrorView m, BatchView b, int pod) {
 }
 
 // k_nominated (one thread, after PreFilter and the pod's histograms): evaluateNominatedNode (schedule_one.go:657-669,
-// 714-745) for status.nominatedNodeName -- that node's filters alone (RunFilterPluginsWithNominatedPods: this
-// context tracks no other pod's nomination).  Feasible: the pod is placed there (schedulePod's one-feasible-node
+// 714-745) for status.nominatedNodeName -- that node's filters alone (RunFilterPluginsWithNominatedPods: with the
+// other pods nominated to it added, run_filters; the pod's own record is never in its G).  Feasible: the pod is placed there (schedulePod's one-feasible-node
 // path, :586-598; nextStartNodeIndex stays).  Else the node's status joins NodeToStatus (kept for evaluation
 // output, counted once by k_sample_find) and the full pass follows.
 __global__ void k_nominated(MirrorView m, BatchView b, int pod) {
@@ -2003,7 +2131,7 @@ __constant__ int8_t kWaveMap[3][kLoopThreads / 64] = {{0, 1, 2, 3, 4, 5}, {4, 0,
 // (the body of k_sched_loop and k_sched_loop_group: w = the workgroup this block plays in its rank)
 // (GRP: the group instance takes w from its block index; the others read blockIdx.x itself, as before the group
 // instance existed -- their register allocation is that sensitive)
-template <int NW, bool RING, int MS, bool GRP>
+template <int NW, bool RING, int MS, bool GRP, bool NOM>
 __device__ __forceinline__ void sched_loop_body(const MirrorView& m, const BatchView& b, const LoopView& lv, const int w_grp) {
   constexpr int U = NW * 64;                  // nodes per unit: one per evaluation-wave lane
   constexpr int kLoopThreads = U + 128;       // NW evaluation waves, one selection wave, one helper wave
@@ -2077,7 +2205,7 @@ __device__ __forceinline__ void sched_loop_body(const MirrorView& m, const Batch
     for (int kk = 0; kk < kLoopMaxBlk; ++kk) {
       const int i = (k0 + kk) * U + t;
       if (kk < nk && i < m.n) {
-        const NodeCore c = load_core(m, i);
+        const NodeCore c = load_core<NOM>(m, i);
         s_core.acpu[kk][t] = c.acpu;
         s_core.amem[kk][t] = c.amem;
         s_core.aeph[kk][t] = c.aeph;
@@ -2181,8 +2309,8 @@ __device__ __forceinline__ void sched_loop_body(const MirrorView& m, const Batch
             int64_t with1 = kNoBal, wo2;
             if (bal) with1 = bal2(c.rcpu + pf.bpr_cpu, c.acpu, c.rmem + pf.bpr_mem, c.amem);
             wo2 = bal && same_bal ? with1 : bal2(c2.rcpu, c2.acpu, c2.rmem, c2.amem);
-            ne = eval_core_fast(m, c, s_core.bwo[kk][t], pf, base, d, i, with1);
-            ne2 = eval_core_fast(m, c2, wo2, pf, base, d, i);
+            ne = eval_core_fast<NOM>(m, c, s_core.bwo[kk][t], pf, base, d, i, with1);
+            ne2 = eval_core_fast<NOM>(m, c2, wo2, pf, base, d, i);
             s_bwo2[kk][t] = wo2;
           }
           const unsigned long long b2 = __ballot(ne2.st == 0);
@@ -2191,8 +2319,8 @@ __device__ __forceinline__ void sched_loop_body(const MirrorView& m, const Batch
           s_rt2[kk][t] = (uint32_t)ne2.rt;
           s_rn2[kk][t] = (uint32_t)ne2.rna;
         } else if (i < m.n) {
-          ne = fast ? eval_core_fast(m, lds_core(s_core, kk, t), s_core.bwo[kk][t], pf, base, d, i)
-                    : eval_node<false>(m, b, base, d, pod, i, true);
+          ne = fast ? eval_core_fast<NOM>(m, lds_core(s_core, kk, t), s_core.bwo[kk][t], pf, base, d, i)
+                    : eval_node<false, NOM>(m, b, base, d, pod, i, true);
         }
         record(kk, ne);
       }
@@ -2743,8 +2871,8 @@ __device__ __forceinline__ void sched_loop_body(const MirrorView& m, const Batch
           lds_put_dynamic(s_core, kw, t, c);
           if (more) {
             const NodeEval ne = (nd.flags & DF_FAST)
-                                    ? eval_core_fast(m, c, s_core.bwo[kw][t], load_fast(nb, nd), nb, nd, win)
-                                    : eval_node<false>(m, b, nb, nd, pod + 1, win, true);
+                                    ? eval_core_fast<NOM>(m, c, s_core.bwo[kw][t], load_fast(nb, nd), nb, nd, win)
+                                    : eval_node<false, NOM>(m, b, nb, nd, pod + 1, win, true);
             feas = ne.st == 0;
             s_fx[npar][kw][t] = ne.fixed;
             s_rt[npar][kw][t] = (uint32_t)ne.rt;
@@ -2791,10 +2919,12 @@ __device__ __forceinline__ void sched_loop_body(const MirrorView& m, const Batch
 }
 // The views are read where the kernel arguments lie (the kernarg segment, laid out as LoopGroupArg): binding the
 // by-value parameters to the body's references made the compiler copy them into registers up front (scratch spills)
-template <int NW, bool RING, int MS = kMaxSweep>
+// NOM: the launch carries a nominee table (MirrorView::nom); launches without one -- the common case -- run the
+// instances compiled without the overlay
+template <int NW, bool RING, int MS = kMaxSweep, bool NOM = false>
 __global__ __launch_bounds__(NW * 64 + 128) void k_sched_loop(MirrorView m, BatchView b, LoopView lv) {
   const LoopGroupArg& a = *(const LoopGroupArg*)__builtin_amdgcn_kernarg_segment_ptr();
-  sched_loop_body<NW, RING, MS, false>(a.m, a.b, a.lv, 0);
+  sched_loop_body<NW, RING, MS, false, NOM>(a.m, a.b, a.lv, 0);
 }
 // In-process rank groups (localGroup: W contexts on one device): every rank's loop in ONE dispatch, block
 // r * G + w playing rank r's workgroup w with rank r's views.  Loops of separate dispatches on separate
@@ -2804,7 +2934,8 @@ template <int NW, int MS>
 __global__ __launch_bounds__(NW * 64 + 128) void k_sched_loop_group(const LoopGroupArg* __restrict__ ga, int G) {
   const int r = (int)blockIdx.x / G;
   const LoopGroupArg& a = ga[r];
-  sched_loop_body<NW, false, MS, true>(a.m, a.b, a.lv, (int)blockIdx.x - r * G);
+  // (node-sharded contexts refuse nominatedPods "Evaluate": no table)
+  sched_loop_body<NW, false, MS, true, false>(a.m, a.b, a.lv, (int)blockIdx.x - r * G);
 }
 
 
@@ -5012,6 +5143,18 @@ hipError_t launch_max_reduce(unsigned long long* dst, const RankPtrs& src, int n
 // unit 128: 128-node workgroups (two evaluation waves, every role on a SIMD of its own); 256: four
 hipError_t launch_sched_loop(const MirrorView& m, const BatchView& b, const LoopView& lv, hipStream_t s,
                              hipEvent_t t0, hipEvent_t t1, int unit) {
+  if (m.nom != nullptr) {  // a nominee table: the instances with the overlay (any number of sweep rounds)
+    const dim3 grid(lv.nwg), blk(unit == 128 ? 2 * 64 + 128 : kLoopThreads);
+    if (lv.ring) {
+      if (unit == 128) hipLaunchKernelGGL((k_sched_loop<2, true, kMaxSweep, true>), grid, blk, 0, s, m, b, lv);
+      else hipLaunchKernelGGL((k_sched_loop<4, true, kMaxSweep, true>), grid, blk, 0, s, m, b, lv);
+    } else if (unit == 128) {
+      hipExtLaunchKernelGGL((k_sched_loop<2, false, kMaxSweep, true>), grid, blk, 0, s, t0, t1, 0, m, b, lv);
+    } else {
+      hipExtLaunchKernelGGL((k_sched_loop<4, false, kMaxSweep, true>), grid, blk, 0, s, t0, t1, 0, m, b, lv);
+    }
+    return hipGetLastError();
+  }
   if (lv.ring) {  // resident (no timing events: the launch spans many calls)
     if (unit == 128 && lv.world * lv.nwg <= 64)
       hipLaunchKernelGGL((k_sched_loop<2, true, 1>), dim3(lv.nwg), dim3(2 * 64 + 128), 0, s, m, b, lv);
@@ -5101,6 +5244,15 @@ hipError_t loop_occupancy(int (&occ)[4]) {
     const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ[i], ks[i].f, ks[i].threads, 0);
     if (e != hipSuccess) return e;
   }
+  // (k_sched_loop's instances with the nominee overlay use more registers: a grid must fit either)
+  const K kn[2] = {{reinterpret_cast<const void*>(&k_sched_loop<2, false, kMaxSweep, true>), 2 * 64 + 128},
+                   {reinterpret_cast<const void*>(&k_sched_loop<4, false, kMaxSweep, true>), kLoopThreads}};
+  for (int i = 0; i < 2; ++i) {
+    int o = 0;
+    const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&o, kn[i].f, kn[i].threads, 0);
+    if (e != hipSuccess) return e;
+    occ[i] = o < occ[i] ? o : occ[i];
+  }
   return hipSuccess;
 }
 // Loads the module's code object onto the current device now (hipFuncGetAttributes), so that no
@@ -5115,6 +5267,10 @@ hipError_t warm_kernels() {
                       reinterpret_cast<const void*>(&k_sched_loop<4, false>), reinterpret_cast<const void*>(&k_sched_loop<2, false>),
                       reinterpret_cast<const void*>(&k_sched_loop<4, true>), reinterpret_cast<const void*>(&k_sched_loop<2, true>),
                       reinterpret_cast<const void*>(&k_sched_loop<2, false, 1>), reinterpret_cast<const void*>(&k_sched_loop<2, true, 1>),         reinterpret_cast<const void*>(&k_sample_find),
+                      reinterpret_cast<const void*>(&k_sched_loop<4, false, kMaxSweep, true>),
+                      reinterpret_cast<const void*>(&k_sched_loop<2, false, kMaxSweep, true>),
+                      reinterpret_cast<const void*>(&k_sched_loop<4, true, kMaxSweep, true>),
+                      reinterpret_cast<const void*>(&k_sched_loop<2, true, kMaxSweep, true>),
                       reinterpret_cast<const void*>(&k_sample_apply),        reinterpret_cast<const void*>(&k_sample_shard_a),
                       reinterpret_cast<const void*>(&k_sample_shard_b),        reinterpret_cast<const void*>(&k_node_update),
                       reinterpret_cast<const void*>(&k_node_dyn),           reinterpret_cast<const void*>(&k_agg_loop<false, false>),
@@ -5551,6 +5707,21 @@ __device__ __forceinline__ int64_t* preempt_sreq(const MirrorView& m, const uint
   return row;
 }
 
+// SelectVictimsOnNode filters through RunFilterPluginsWithNominatedPods too: the dry run's core (and its scratch of
+// the preemptor's scalar resources) is the node's plus G before the victims come off -- nominees have priority >=
+// the preemptor's, so none is a victim.  Returns whether one of G's host ports conflicts with the preemptor's.
+__device__ __forceinline__ bool preempt_nominees(const MirrorView& m, const uint8_t* base, const PodDesc& d, int i,
+                                                 NodeCore* nc, int64_t* sreq) {
+  if (m.nom == nullptr || !(nc->flags & NF_NOMINEES)) return false;
+  const NomG g = nom_gather(m, base, d, i);
+  *nc = nom_core(*nc, g);
+  if (sreq) {
+    const ScalarReq* sr = at<ScalarReq>(base, d.scalar_off);
+    for (int k = 0; k < d.n_scalar; ++k) sreq[k] += nom_scalar(m, d, g, sr[k].slot);
+  }
+  return g.port;
+}
+
 // Host-staged victims (PNode / PVictim: the host sorted them and grouped them by PDB violation)
 template <class S>
 __global__ __launch_bounds__(kBlock) void k_preempt(MirrorView m, BatchView b, int pod, const PNode* pn,
@@ -5582,6 +5753,7 @@ __global__ __launch_bounds__(kBlock) void k_preempt(MirrorView m, BatchView b, i
   NodeCore nc = load_core(m, i);
   int64_t* sreq = preempt_sreq(m, base, d, in, i);
   const int ns = d.n_scalar;
+  const bool nom_port = preempt_nominees(m, base, d, i, &nc, sreq);
   TopoTrack<S> T;
   topo_track_init(m, b, pod, base, d, i, in, T, &o.flags);
   const PVictim* v = pv + nd.voff;
@@ -5595,7 +5767,7 @@ __global__ __launch_bounds__(kBlock) void k_preempt(MirrorView m, BatchView b, i
     moves |= topo_victim(m, base, d, in, T, v[q].slot, -1);
   }
   nc.npods -= nd.vcnt;
-  bool port = (nd.flags & PN_BASE_PORT) != 0;
+  bool port = (nd.flags & PN_BASE_PORT) != 0 || nom_port;
   uint32_t st = preempt_node_filters(m, nc, sreq, nullptr, base, d, i, port);
   if (st == 0) st = topo_filters(m, base, d, i, T.tp, 0);
   o.st = st;
@@ -5721,6 +5893,7 @@ __global__ __launch_bounds__(kBlock) void k_preempt_seg(MirrorView m, BatchView 
     }
   NodeCore nc = load_core(m, i);
   int64_t* sreq = preempt_sreq(m, base, d, in, i);
+  port |= preempt_nominees(m, base, d, i, &nc, sreq);
   auto vsc = [&](const PRec& x) -> const int64_t* {  // the victim's request of the preemptor's scalars
     return sreq && (x.flags & PR_SCALAR) ? in.vsc + (size_t)x.slot * ns : nullptr;
   };

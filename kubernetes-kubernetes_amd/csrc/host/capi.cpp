@@ -47,6 +47,8 @@ static int with_err(ksg_ctx* ctx, int rc) {
   return rc;
 }
 
+static ksg_result not_scheduled() { return ksg_result{KSG_CODE_ERROR, -1, 0, 0, 0}; }
+
 extern "C" {
 
 ksg_ctx* ksg_create(const char* config_json, size_t len) {
@@ -80,6 +82,12 @@ ksg_ctx* ksg_create(const char* config_json, size_t len) {
       return nullptr;
     }
     if (cfg.sharded()) {  // node-sharded: join the exchange group (collective across the ranks)
+      if (cfg.nominated_evaluate) {  // (every rank has the same config, so all fail here)
+        g_create_error = "nominatedPods \"Evaluate\" on a node-sharded context: the sharded loops do not filter with "
+                         "nominated pods; use \"Refuse\" (the default)";
+        delete ctx;
+        return nullptr;
+      }
       if (ctx->engine->ob_acting()) {  // before the collective: every rank has the same profile, so all fail here
         g_create_error = "OpportunisticBatching acts in this profile (PodTopologySpread without default constraints) "
                          "and the node-sharded scheduler does not run it: set featureGates.OpportunisticBatching false";
@@ -255,7 +263,10 @@ int ksg_schedule_one(ksg_ctx* ctx, int32_t handle, uint32_t flags, ksg_result* r
     auto it = ctx->engine->queue.find(handle);
     if (it == ctx->engine->queue.end()) return KSG_ENOTFOUND;
     if (const int rn = ctx->engine->check_nominations({&it->second})) return with_err(ctx, rn);
-    if (!eval && (flags & KSG_FLAG_ASSUME)) {  // a resident loop (k_sched_loop / k_agg_loop), else the launch path
+    // (a pod the nominator holds ends its nomination when it is assumed: the nominee table changes, which a
+    // resident loop does not see -- it takes the launch path)
+    const bool owner = ctx->engine->nom_evaluate() && ctx->engine->nom_owner(it->second);
+    if (!eval && (flags & KSG_FLAG_ASSUME) && !owner) {  // a resident loop (k_sched_loop / k_agg_loop), else the launch path
       bool handled = false;
       const int rc = ctx->engine->schedule_resident(it->second, handle, result, &handled);
       if (handled) return with_err(ctx, rc);
@@ -281,7 +292,26 @@ int ksg_schedule_batch(ksg_ctx* ctx, const int32_t* handles, int32_t n, uint32_t
       pods.push_back(&it->second);
     }
     if (const int rn = ctx->engine->check_nominations(pods)) return with_err(ctx, rn);
-    return with_err(ctx, ctx->engine->run_batch_api(pods, hs, (flags & KSG_FLAG_ASSUME) != 0, results, nullptr));
+    const bool assume = (flags & KSG_FLAG_ASSUME) != 0;
+    // nominatedPods "Evaluate": pod i sees the nominator as pods 0..i-1 left it, and an assume ends the assumed
+    // pod's own nomination.  The nominee table is staged per run, so a run ends after every pod the nominator
+    // holds; the pods between them -- nearly always the whole batch -- run as one.
+    if (ctx->engine->nom_evaluate() && assume && !ctx->engine->nominated.empty()) {
+      int32_t a = 0;
+      for (int32_t i = 0; i < n; ++i) {
+        if (i + 1 < n && !ctx->engine->nom_owner(*pods[(size_t)i])) continue;
+        const std::vector<const PodSpec*> sub(pods.begin() + a, pods.begin() + i + 1);
+        const std::vector<int32_t> sh(hs.begin() + a, hs.begin() + i + 1);
+        const int rc = ctx->engine->run_batch_api(sub, sh, assume, results + a, nullptr);
+        if (rc != KSG_OK) {  // as a loop give-up leaves a batch: the pods after the failed run are not scheduled
+          for (int32_t j = i + 1; j < n; ++j) results[j] = not_scheduled();
+          return with_err(ctx, rc);
+        }
+        a = i + 1;
+      }
+      return with_err(ctx, KSG_OK);
+    }
+    return with_err(ctx, ctx->engine->run_batch_api(pods, hs, assume, results, nullptr));
   })
 }
 
@@ -306,16 +336,22 @@ int ksg_add_nominated_pod(ksg_ctx* ctx, const char* pod_json, size_t len) {  // 
       ctx->err = "ksg_add_nominated_pod: metadata.uid is empty";
       return KSG_EINVAL;
     }
-    ctx->engine->nominated.erase(p.uid);  // deleteUnlocked: at most one nomination per uid
-    if (!p.nominated_node.empty()) ctx->engine->nominated[p.uid] = std::make_pair(p.nominated_node, p.priority);
+    // (a resident loop reads the nominee table it was launched with)
+    if (ctx->engine->nom_evaluate())
+      if (const int rs = quiesce(ctx)) return rs;
+    ctx->engine->nominate(p);
     return KSG_OK;
   })
 }
 
 int ksg_delete_nominated_pod(ksg_ctx* ctx, const char* uid) {  // nominator.go:138-...
   if (!ctx || !uid) return KSG_EINVAL;
-  ctx->engine->nominated.erase(uid);
-  return KSG_OK;
+  GUARD({
+    if (ctx->engine->nom_evaluate())
+      if (const int rs = quiesce(ctx)) return rs;
+    ctx->engine->denominate(uid);
+    return KSG_OK;
+  })
 }
 
 int ksg_run_filter_plugin(ksg_ctx* ctx, int32_t handle, int32_t plugin, int32_t* prefilter_code, uint8_t* codes,

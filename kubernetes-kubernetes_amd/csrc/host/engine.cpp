@@ -338,6 +338,14 @@ int Engine::compile(const PodSpec& p, Mode mode, int plugin, bool assume, bool e
       D.nominated_node = ix;
     }
   }
+  // other pods' nominations (the nominee table as nom_prepare left it): the pod's priority selects G(p, n), its
+  // own record is never in it
+  D.nom_self = -1;
+  if (mode == CYCLE && nom_active_) {
+    D.nom_prio = p.priority;
+    auto it = nom_index_.find(p.uid);
+    if (it != nom_index_.end()) D.nom_self = it->second;
+  }
 
   // TaintToleration: per distinct taint, "not tolerated" bits (taint_toleration.go:102-196)
   bool any_intol = false;  // some PreferNoSchedule taint of the cluster is not tolerated (raw scores can be > 0)
@@ -1250,7 +1258,7 @@ Engine::~Engine() {
   for (DevBuf* b : {&d_descs, &d_meta, &d_status, &d_fmask, &d_blk, &d_fixed, &d_raw, &d_out,
                     &d_total, &d_arena, &d_xa, &d_xp, &d_xb, &d_xs, &d_gran, &d_fail, &d_grp, &d_agran, &d_region, &d_astamps, &d_aspill, &d_relay,
                     &d_evg, &d_aggpeers, &d_pre, &d_seg, &d_segcnt, &d_psout, &d_pdb, &d_pick, &d_contrib_buf, &d_wide, &d_vsc,
-                    &d_ob, &d_ob_heap, &d_ob_map, &d_tcache, &d_tcw})
+                    &d_ob, &d_ob_heap, &d_ob_map, &d_tcache, &d_tcw, &d_nom})
     if (b->p) (void)hipFree(b->p);
   if (h_pinned) (void)hipHostFree(h_pinned);
   if (h_tcw) (void)hipHostFree(h_tcw);
@@ -1642,21 +1650,166 @@ int Engine::group_launch(GroupReq* req, bool agg, int nwg, int unit) {
 }
 
 // RunFilterPluginsWithNominatedPods (framework.go:1211-1294) filters a node with the pods nominated to it of equal or
-// higher priority added (addGENominatedPods: corev1.PodPriority >= the pod's, another uid), which this library does
-// not run: a call in which some pod would see such a nomination on a snapshot node is refused before anything runs.
+// higher priority added (addGENominatedPods: corev1.PodPriority >= the pod's, another uid); if that pass succeeds it
+// filters the node again as it is, and that status is the node's.
+// nominatedPods "Refuse" (the default) runs neither: a call in which some pod would see such a nomination on a
+// snapshot node is refused before anything runs.
+// "Evaluate" filters on the device with the node's core plus those pods (the nominee table, nom_status in
+// kernels.hip) and scores on the core as it is.  One pass is exact for every pair in which NodeResourcesFit and
+// NodePorts are the only filters that read what the added pods change, both monotone in the pods added (a node
+// that passes with them passes without them).  The pairs in which PodTopologySpread or InterPodAffinity would read
+// them are still refused, the call as a whole, before anything runs: the pod has (a) a DoNotSchedule spread
+// constraint (its own or a profile default) or (b) a required pod affinity / anti-affinity term, or (c) a pod it
+// would see added has a required anti-affinity term (InterPodAffinity's existing-pod check).  A batch is judged
+// against the nominator as the call found it.
 int Engine::check_nominations(const std::vector<const PodSpec*>& pods) {
   if (nominated.empty()) return KSG_OK;
   c->order();  // (the snapshot's index, current)
-  for (const PodSpec* p : pods)
+  const bool evaluate = nom_evaluate();
+  for (const PodSpec* p : pods) {
+    const Nominee* seen = nullptr;
+    const std::string* seen_uid = nullptr;
+    bool anti = false;
     for (const auto& kv : nominated)
-      if (kv.first != p->uid && kv.second.second >= p->priority && c->index_of(kv.second.first) >= 0) {
-        c->err = "pod " + p->ns + "/" + p->name + ": pod uid " + kv.first + " (priority " + std::to_string(kv.second.second) +
-                 ") is nominated to node " + kv.second.first +
-                 "; filtering with nominated pods (RunFilterPluginsWithNominatedPods) runs outside the device path";
-        return KSG_ENOTSUP;
+      if (kv.first != p->uid && kv.second.priority >= p->priority && c->index_of(kv.second.node) >= 0) {
+        if (!seen || (kv.second.req_anti && !anti)) {
+          seen = &kv.second;
+          seen_uid = &kv.first;
+        }
+        anti = anti || kv.second.req_anti;
+        if (!evaluate) break;
       }
+    if (!seen) continue;
+    const std::string who = "pod " + p->ns + "/" + p->name + ": pod uid " + *seen_uid + " (priority " +
+                            std::to_string(seen->priority) + ") is nominated to node " + seen->node;
+    if (!evaluate) {
+      c->err = who + "; filtering with nominated pods (RunFilterPluginsWithNominatedPods) runs outside the device path";
+      return KSG_ENOTSUP;
+    }
+    bool dns = false;  // a DoNotSchedule constraint applies: its own, or (none of its own) a profile default
+    for (const Spread& sp : p->spreads) dns = dns || sp.when == "DoNotSchedule";
+    if (p->spreads.empty())
+      for (const Spread& sp : c->cfg.pts_defaults) dns = dns || sp.when == "DoNotSchedule";
+    const char* why = nullptr;
+    if (dns)
+      why = "(a) the pod has a DoNotSchedule topology spread constraint, whose counts the nominated pod may move";
+    else if ((p->has_pod_affinity && !p->aff_req.empty()) || (p->has_pod_anti && !p->anti_req.empty()))
+      why = "(b) the pod has a required pod affinity or anti-affinity term, whose counts the nominated pod may move";
+    else if (anti)
+      why = "(c) the nominated pod has a required pod anti-affinity term, which InterPodAffinity would check against the pod";
+    if (why) {
+      c->err = who + "; " + why + " (RunFilterPluginsWithNominatedPods for such a pair runs outside the device path)";
+      return KSG_ENOTSUP;
+    }
+  }
   return KSG_OK;
 }
+
+bool Engine::nom_evaluate() const { return c->cfg.nominated_evaluate; }
+
+void Engine::nominate(const PodSpec& p) {
+  nominated.erase(p.uid);  // deleteUnlocked: at most one nomination per uid
+  nom_dirty_ = true;
+  if (p.nominated_node.empty()) return;
+  Nominee nm;
+  nm.node = p.nominated_node;
+  nm.priority = p.priority;
+  if (nom_evaluate()) {  // what NodeInfo.AddPodInfo adds to the node (framework/types.go:1035-1076, 445-468)
+    const PodResources r = calc_resources(p);
+    nm.cpu = r.cpu;
+    nm.mem = r.mem;
+    nm.eph = r.eph;
+    for (const auto& sv : r.scalar)
+      if (sv.second != 0) nm.scalar.push_back({c->scalar_slot(sv.first), sv.second});
+    auto take = [&](const Container& k) {
+      for (const HostPort& hp : k.ports)
+        if (hp.port > 0) nm.ports.push_back(c->port_id(hp.ip, hp.proto, hp.port));
+    };
+    for (const Container& k : p.init_containers)
+      if (k.sidecar) take(k);
+    for (const Container& k : p.containers) take(k);
+    nm.req_anti = !p.anti_req.empty();
+  }
+  nominated.emplace(p.uid, std::move(nm));
+}
+
+void Engine::denominate(const std::string& uid) {
+  if (nominated.erase(uid)) nom_dirty_ = true;
+}
+
+void Engine::nom_prepare() {
+  if (!nom_evaluate()) return;
+  c->order();
+  if (!nom_dirty_ && nom_list_gen_ == c->list_gen) return;
+  nom_dirty_ = false;
+  nom_list_gen_ = c->list_gen;
+  nom_upload_ = true;
+  nom_index_.clear();
+  struct Ent { int32_t node; const std::string* uid; const Nominee* nm; };
+  std::vector<Ent> ents;
+  for (const auto& kv : nominated) {
+    const int32_t ix = c->index_of(kv.second.node);
+    if (ix >= 0) ents.push_back({ix, &kv.first, &kv.second});
+  }
+  nom_active_ = !ents.empty();
+  nom_host_.clear();
+  if (!nom_active_) return;
+  std::sort(ents.begin(), ents.end(), [](const Ent& a, const Ent& b) {
+    if (a.node != b.node) return a.node < b.node;
+    if (a.nm->priority != b.nm->priority) return a.nm->priority > b.nm->priority;
+    return *a.uid < *b.uid;
+  });
+  const size_t N = c->order().size();
+  std::vector<int32_t> head(N + 1, 0);
+  std::vector<NomRec> recs(ents.size());
+  std::vector<uint32_t> ports;
+  std::vector<ScalarReq> scs;
+  for (size_t q = 0; q < ents.size(); ++q) {
+    const Nominee& nm = *ents[q].nm;
+    head[(size_t)ents[q].node + 1]++;
+    NomRec& r = recs[q];
+    r = NomRec{};
+    r.cpu = nm.cpu;
+    r.mem = nm.mem;
+    r.eph = nm.eph;
+    r.prio = nm.priority;
+    r.port_lo = (int32_t)ports.size();
+    r.port_cnt = (int32_t)nm.ports.size();
+    ports.insert(ports.end(), nm.ports.begin(), nm.ports.end());
+    r.sc_lo = (int32_t)scs.size();
+    r.sc_cnt = (int32_t)nm.scalar.size();
+    for (const auto& sv : nm.scalar) scs.push_back(ScalarReq{sv.first, 0, sv.second});
+    nom_index_[*ents[q].uid] = (int32_t)q;
+  }
+  for (size_t i = 0; i < N; ++i) head[i + 1] += head[i];
+  auto up16 = [](size_t v) { return (v + 15) & ~size_t(15); };
+  NomHdr h{};
+  h.n_rec = (int32_t)recs.size();
+  h.rec_off = (int32_t)up16(sizeof(NomHdr) + head.size() * 4);
+  h.port_off = (int32_t)up16((size_t)h.rec_off + recs.size() * sizeof(NomRec));
+  h.sc_off = (int32_t)up16((size_t)h.port_off + ports.size() * 4);
+  nom_host_.assign(up16((size_t)h.sc_off + scs.size() * sizeof(ScalarReq)) + 16, 0);
+  std::memcpy(nom_host_.data(), &h, sizeof(h));
+  std::memcpy(nom_host_.data() + sizeof(NomHdr), head.data(), head.size() * 4);
+  std::memcpy(nom_host_.data() + h.rec_off, recs.data(), recs.size() * sizeof(NomRec));
+  if (!ports.empty()) std::memcpy(nom_host_.data() + h.port_off, ports.data(), ports.size() * 4);
+  if (!scs.empty()) std::memcpy(nom_host_.data() + h.sc_off, scs.data(), scs.size() * sizeof(ScalarReq));
+}
+
+int Engine::nom_sync() {
+  if (!nom_evaluate()) return KSG_OK;
+  if (nom_upload_ && nom_active_) {
+    int rc;
+    if ((rc = ensure(d_nom, nom_host_.size()))) return rc;
+    HIPCHK(hipMemcpyAsync(d_nom.p, nom_host_.data(), nom_host_.size(), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));  // pageable source
+  }
+  nom_upload_ = false;
+  c->view.nom = nom_active_ ? (const uint8_t*)d_nom.p : nullptr;
+  return KSG_OK;
+}
+
+void Engine::nom_off() { c->view.nom = nullptr; }
 
 int Engine::run_batch_api(const std::vector<const PodSpec*>& pods, const std::vector<int32_t>& handles, bool assume,
                           ksg_result* results, ksg_eval_out* eval) {
@@ -1716,6 +1869,7 @@ int Engine::run_batch(const std::vector<const PodSpec*>& pods, const std::vector
   } nom_reset{&nom_batch_};
   for (int i = 0; i < n && !nom_batch_; ++i) nom_batch_ = !pods[i]->nominated_node.empty();
   c->order();
+  nom_prepare();
   if (c->order().empty()) {  // ErrNoNodesAvailable (schedule_one.go:569-571)
     for (int i = 0; i < n; ++i) results[i] = ksg_result{KSG_CODE_ERROR, -1, 0, 0, 0};
     return KSG_OK;
@@ -1867,6 +2021,7 @@ int Engine::run_batch(const std::vector<const PodSpec*>& pods, const std::vector
   const auto Tm = clk::now();
   htrace("mirror");
   if ((rc = c->ensure_mirror(pods_needed))) return rc;
+  if ((rc = nom_sync())) return rc;
   if (ob_acting() && (rc = ob_sync(c->stream))) return rc;
   mirror_us_ = std::chrono::duration<double, std::micro>(clk::now() - Tm).count();
   // ---- staging: [offsets n | program sizes n | PodStats n | DevResult n | give-up flags n | programs]
@@ -2152,7 +2307,7 @@ int Engine::run_batch(const std::vector<const PodSpec*>& pods, const std::vector
         int rc2 = c->add_pod(*pods[i], uid, /*device_done=*/!foreign, cp[i].slot, &c->order()[r.node_index], &cp[i].res);
         if (rc2) return rc2;
         assumed[handles.empty() ? -1 : handles[i]] = uid;
-        nominated.erase(pods[i]->uid);  // an assumed pod's nomination ends (schedule_one.go:1131-1134)
+        denominate(pods[i]->uid);  // an assumed pod's nomination ends (schedule_one.go:1131-1134)
       } else {
         c->pod_table_drop(cp[i].slot);  // not placed: the reserved pod-table slot never went live
       }
@@ -2254,6 +2409,7 @@ int Engine::run_batch(const std::vector<const PodSpec*>& pods, const std::vector
       }
       regate = true;
       if ((r2 = c->ensure_mirror())) return r2;
+      if ((r2 = nom_sync())) return r2;
       arena_words = std::max(arena_words, aw);
       o = 0;
       if ((r2 = ensure_scratch(std::max(need, desc_bytes), n, false, arena_words))) return r2;
@@ -2963,6 +3119,7 @@ int Engine::run_plugin(const PodSpec& p, Mode mode, int plugin, const uint8_t* n
     return KSG_OK;
   }
   if ((rc = c->ensure_mirror())) return rc;
+  nom_off();  // one plugin run alone (RunFilterPlugins / RunScorePlugins of the shim): no nominated pod is added
   if ((rc = ensure_scratch(cp.blob.size(), 1, true, cp.arena_words))) return rc;
   uint8_t* hp = (uint8_t*)h_pinned;
   std::memcpy(hp, cp.blob.data(), cp.blob.size());
@@ -3145,6 +3302,7 @@ int Engine::schedule_resident(const PodSpec& p, int32_t handle, ksg_result* res,
   if (!sched_geo && !agg_geo) return KSG_OK;
   // PreFilter / PreScore on the host, as run_batch's compile_upto
   const auto T0 = clk::now();
+  nom_prepare();
   CompiledPod cp;
   int rc = compile(p, CYCLE, -1, true, false, &cp);
   if (rc) {
@@ -3221,13 +3379,14 @@ int Engine::schedule_resident(const PodSpec& p, int32_t handle, ksg_result* res,
   bool reposted = false;
 relaunch:
   // the running launch sees the mirror as it is, or it stops (so does a launch of the other kind)
-  if (res_running_ && (c->mirror_pending() || res_q_ >= kLoopMaxPods || res_kind_ != kind ||
+  if (res_running_ && (c->mirror_pending() || nom_stale() || res_q_ >= kLoopMaxPods || res_kind_ != kind ||
                        (kind == 1 && (GS != res_gs_ || unit != res_unit_)) || (kind == 2 && G != res_gs_) ||
                        (kind == 2 && res_terms_ + cp.own_terms > kRingTermBudget) ||
                        clk::now() - res_last_ > std::chrono::milliseconds(kResidentIdleMs / 2)))
     if ((rc = resident_stop())) return fail(rc);
   if (!res_running_) {
     if ((rc = c->ensure_mirror(kind == 2))) return fail(rc);
+    if ((rc = nom_sync())) return fail(rc);
     if (kind == 2 && cp.slot >= 0) {  // (the upload may have moved the label pool: the entry again)
       entry_bytes = c->ring_entry(cp.slot, entry, kRingEntryBytes);
       if (entry_bytes == 0) {
@@ -3520,7 +3679,7 @@ relaunch:
     if ((rc = c->add_pod(p, uid, /*device_done=*/true, cp.slot, &c->order()[(size_t)res->node_index], &cp.res)))
       return rc;
     assumed[handle] = uid;
-    nominated.erase(p.uid);  // (schedule_one.go:1131-1134)
+    denominate(p.uid);  // (schedule_one.go:1131-1134)
   } else {
     c->pod_table_drop(cp.slot);
   }

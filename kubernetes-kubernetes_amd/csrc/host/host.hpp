@@ -224,6 +224,7 @@ struct Config {
                                 // between calls, fed through a host-pinned pod ring ("residentLoop")
   bool agg_loop = true;         // runs of PTS/IPA pods go through k_agg_loop (with persistent_loop)
   int agg_debug = 0;            // AggView::debug (diagnostic)
+  bool nominated_evaluate = false;  // "nominatedPods": "Evaluate" (default "Refuse"), DESIGN.md §4.10
   // resident loops: relay the doorbell through device memory from this many workgroups on (one PCIe poller instead
   // of G; round 6, profiles/r06d_resident_ab.txt: C2's 40 workgroups 19.8 -> 14.8 us per call, DTS's 20 27.0 -> 25.3)
   int ring_relay_min = 2;
@@ -533,11 +534,36 @@ class Engine {
   Cluster* c;
   std::unordered_map<int32_t, PodSpec> queue;  // handle -> compiled-for-API pod (find / insert / erase only)
   std::unordered_map<int32_t, std::string> assumed;  // handle -> uid
-  // the nominator (ksg_add_nominated_pod): pod uid -> (nominated node name, spec.priority)
-  std::unordered_map<std::string, std::pair<std::string, int32_t>> nominated;
-  // KSG_ENOTSUP (+ err) when a pod of the call would see another pod's nomination of equal or higher priority on a
-  // snapshot node (RunFilterPluginsWithNominatedPods, not run here)
+  // the nominator (ksg_add_nominated_pod): pod uid -> its nominated node, spec.priority and what
+  // NodeInfo.AddPodInfo would add to that node (kept for config nominatedPods "Evaluate")
+  struct Nominee {
+    std::string node;
+    int32_t priority = 0;
+    int64_t cpu = 0, mem = 0, eph = 0;                   // PodInfo.CalculateResource (Requested)
+    std::vector<std::pair<int32_t, int64_t>> scalar;     // (mirror column, quantity)
+    std::vector<uint32_t> ports;                         // host-port ids (Cluster::port_id)
+    bool req_anti = false;                               // a required pod anti-affinity term
+  };
+  std::unordered_map<std::string, Nominee> nominated;
+  void nominate(const PodSpec& p);        // AddNominatedPod / UpdateNominatedPod (none named: forgotten)
+  void denominate(const std::string& uid);
+  // RunFilterPluginsWithNominatedPods.  nominatedPods "Refuse": KSG_ENOTSUP (+ err) when a pod of
+  // the call would see another pod's nomination of equal or higher priority on a snapshot node.  "Evaluate": the
+  // device filters such a node with those pods added (MirrorView::nom), and the call is refused only when the
+  // nominees could move a topology count the pod's Filter reads: the pod has (a) a DoNotSchedule spread
+  // constraint or (b) a required pod (anti-)affinity term, or (c) one of the nominees has a required
+  // anti-affinity term.  Refused before anything runs; err names the pod and the condition.
   int check_nominations(const std::vector<const PodSpec*>& pods);
+  bool nom_evaluate() const;              // config nominatedPods "Evaluate"
+  bool nom_owner(const PodSpec& p) const { return nominated.count(p.uid) != 0; }
+  // The nominee table.  nom_prepare (before a call's first compile): the host copy, rebuilt when the nominator or
+  // the snapshot's node list changed -- records grouped by snapshot index, by priority descending within a node;
+  // nom_sync (after ensure_mirror, no loop running): the device copy and MirrorView::nom (nullptr: no record);
+  // nom_off: calls that run one plugin alone see no nominated pod.
+  void nom_prepare();
+  int nom_sync();
+  void nom_off();
+  bool nom_stale() const { return nom_upload_; }  // a running resident loop reads an older table: it stops first
   int32_t next_handle = 1;
 
   enum Mode { CYCLE, FILTER_ONE, SCORE_ONE };
@@ -646,6 +672,11 @@ class Engine {
   DevBuf d_pre;              // k_preempt: per-node records, victims, per-node results, victim flags
   // k_preempt_seg: every node's pods as an importance-ordered segment (host copy + identities)
   DevBuf d_seg, d_segcnt, d_psout, d_pdb, d_pick, d_contrib_buf, d_wide;
+  DevBuf d_nom;  // the nominee table (NomHdr, heads, records, port ids, scalar requests)
+  std::vector<uint8_t> nom_host_;
+  std::unordered_map<std::string, int32_t> nom_index_;  // uid -> its record (nominees on snapshot nodes)
+  bool nom_dirty_ = true, nom_upload_ = false, nom_active_ = false;
+  uint64_t nom_list_gen_ = ~0ull;
   DevBuf d_vsc;  // preemption: the pods' requests of the preemptor's extended resources + the per-node scratch
   std::vector<PRec> h_seg;
   std::vector<int32_t> h_segcnt;

@@ -894,6 +894,14 @@ bool decode_config(const char* p, size_t n, Config* c, std::string* err) {
     c->loop_unit = (int)d.num(r, "loopUnit", 128) == 256 ? 256 : 128;
     if (const JVal* al = d.get(r, "aggLoop")) c->agg_loop = al->type == JVal::BOOL && al->b;
     c->agg_debug = (int)d.num(r, "aggLoopDebug", 0);
+    if (d.present(r, "nominatedPods")) {  // other pods' nominations: refuse the call, or filter with them added
+      const std::string np = d.str(r, "nominatedPods");
+      if (np != "Refuse" && np != "Evaluate") {
+        *err = "nominatedPods: Unsupported value \"" + np + "\" (\"Refuse\" or \"Evaluate\")";
+        return false;
+      }
+      c->nominated_evaluate = np == "Evaluate";
+    }
     c->ring_relay_min = (int)d.num(r, "ringRelayMinWorkgroups", 2);
     c->debug_give_up_at = (int)d.num(r, "debugLoopGiveUpAt", -1);
     c->loop_wave_map = (int)d.num(r, "loopWaveMap", 0);

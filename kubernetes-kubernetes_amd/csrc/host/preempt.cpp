@@ -298,6 +298,7 @@ int Engine::preempt(const PodSpec& p, const char* args_json, size_t args_len, ks
   }
   const std::vector<std::string>& order = c->order();
   const int32_t N = (int32_t)order.size();
+  nom_prepare();  // SelectVictimsOnNode filters with the nominated pods too (preemption.go:285-343)
   CompiledPod cp;
   int rc = compile(p, CYCLE, -1, false, true, &cp);
   if (rc) return rc;
@@ -309,6 +310,7 @@ int Engine::preempt(const PodSpec& p, const char* args_json, size_t args_len, ks
   const bool ports_on = (D.filter_mask >> P_PORTS) & 1u;
   int32_t nom_ix = p.nominated_node.empty() ? -1 : c->index_of(p.nominated_node);
   if (N > 0 && (rc = c->ensure_mirror())) return rc;
+  if (N > 0 && (rc = nom_sync())) return rc;
   // The device-resident segments serve every pod whose victims' order the cache already knows (no pod
   // sorted by the call's clock, see seg_build) and that the device groups itself: at most kMaxPdb budgets.
   // The rest take the host-staged records (the same per-node core, k_preempt).
