@@ -2125,16 +2125,28 @@ constexpr int kLoopThreads = kBlock + 128;  // NW = 4: four evaluation waves, on
 // map 0 pairs the selection wave with evaluation wave 0, map 1 with the helper, map 2 runs it alone
 // (two evaluation waves then share a SIMD).
 __constant__ int8_t kWaveMap[3][kLoopThreads / 64] = {{0, 1, 2, 3, 4, 5}, {4, 0, 1, 2, 5, 3}, {0, 1, 4, 3, 5, 2}};
+// The split instance (SPLIT, NW = 2; roles: 0-1 "as it is" evaluation, 2 selection, 3 helper, 4-5 "post"
+// evaluation -- the node as if the previous pod landed on it; post wave r owns as-is wave r's slots).  Six waves
+// on four SIMDs: map 0 pairs as-is wave r with post wave r and leaves the selection and the helper wave alone on
+// theirs; map 1 gives the four evaluation waves a SIMD each, the selection and the helper wave (hardware waves 4
+// and 5) each sharing one with a post wave.  Phase 1 ends at the same time under both (1.9 us instead of 3.3 at
+// C2); map 1 stretches phase 2 and the sweeps by the post wave beside them (4.52 against 4.21 us per pod).
+__constant__ int8_t kSplitWaveMap[2][6] = {{0, 1, 2, 3, 4, 5}, {4, 5, 0, 1, 2, 3}};
+// SPLIT: phase 1's two evaluations of a node (against the cores as they are, and with the previous pod assumed)
+// on separate waves instead of one after the other in the same lane.
 // RING: the resident instance (pods through lv.ring, one run per pod); the batch instance has no run
 // loop at all (its one run is the whole launch), so its code is what it was before the ring existed.
 // MS: sweep rounds of 64 participants (the one-round instance for grids of at most 64: no masked-off rounds)
 // (the body of k_sched_loop and k_sched_loop_group: w = the workgroup this block plays in its rank)
 // (GRP: the group instance takes w from its block index; the others read blockIdx.x itself, as before the group
 // instance existed -- their register allocation is that sensitive)
-template <int NW, bool RING, int MS, bool GRP, bool NOM>
+template <int NW, bool RING, int MS, bool GRP, bool NOM, bool SPLIT = false>
 __device__ __forceinline__ void sched_loop_body(const MirrorView& m, const BatchView& b, const LoopView& lv, const int w_grp) {
+  static_assert(!SPLIT || (NW == 2 && !RING && !GRP && !NOM), "the split instance: unsharded 128-node-unit batch runs");
   constexpr int U = NW * 64;                  // nodes per unit: one per evaluation-wave lane
-  constexpr int kLoopThreads = U + 128;       // NW evaluation waves, one selection wave, one helper wave
+  // NW evaluation waves, one selection wave, one helper wave (SPLIT: and NW post-evaluation waves)
+  constexpr int kLoopThreads = U + 128 + (SPLIT ? U : 0);
+  constexpr int kPost0 = NW + 2;              // SPLIT: the first post-evaluation role
   __shared__ __align__(16) uint8_t s_blob[3][kBlobLds];  // pod p's program in s_blob[p % 3]
   __shared__ LoopCoresT<U> s_core;
   __shared__ unsigned long long s_ball[2][kLoopMaxBlk][NW];  // [pod parity]
@@ -2173,12 +2185,15 @@ __device__ __forceinline__ void sched_loop_body(const MirrorView& m, const Batch
   const int k0 = ub0 + (int)((int64_t)unb * w / G), k1 = ub0 + (int)((int64_t)unb * (w + 1) / G);
   const int nk = k1 - k0;  // <= kLoopMaxBlk (host-checked)
   const int lane = threadIdx.x & 63;
-  // my role (NW = 2: one wave per SIMD, no placement to choose)
-  const int wave = NW == 4 ? __builtin_amdgcn_readfirstlane((int)kWaveMap[lv.wave_map][threadIdx.x >> 6])
-                           : (int)(threadIdx.x >> 6);
+  // my role (NW = 2 unsplit: one wave per SIMD, no placement to choose)
+  const int wave = SPLIT   ? __builtin_amdgcn_readfirstlane((int)kSplitWaveMap[lv.wave_map == 1 ? 1 : 0][threadIdx.x >> 6])
+                   : NW == 4 ? __builtin_amdgcn_readfirstlane((int)kWaveMap[lv.wave_map][threadIdx.x >> 6])
+                             : (int)(threadIdx.x >> 6);
   const int vt = wave * 64 + lane;           // my thread index in role order
   const bool sel = wave == NW;      // the selection wave: exchanges + phase 2
   const bool hlp = wave == NW + 1;  // the helper wave: candidate pre-evaluation + staging
+  // SPLIT: a post-evaluation wave (t >= U: it enters none of the evaluation waves' t < U paths)
+  const bool pst = SPLIT && wave >= kPost0;
   const int t = vt;                          // evaluation waves: my slot in each block of my range
   // diagnostic stamps (loopStamps): the resident instance has them in the diagnostic library only (registers)
 #ifdef KSG_DIAG
@@ -2272,7 +2287,9 @@ __device__ __forceinline__ void sched_loop_body(const MirrorView& m, const Batch
     const uint8_t* base = s_blob[slot];
     const PodDesc& d = *reinterpret_cast<const PodDesc*>(base);
     const bool fast = (d.flags & DF_FAST) != 0;
-    const bool post = dprev && post_ok(*dprev, d);
+    // (SPLIT: the post evaluation is the post waves' phase1_post; this wave's is the plain one -- post_ok pods are
+    // DF_FAST, and eval_core_fast forms the BalancedAllocation score with the pod itself, the same bits)
+    const bool post = !SPLIT && dprev && post_ok(*dprev, d);
     const PodFast pf = load_fast(base, d);
     const bool bal = ((pf.sm >> P_BAL) & 1u) != 0;
     const bool same_bal = post && dprev->a_cpu == pf.bpr_cpu && dprev->a_mem == pf.bpr_mem;
@@ -2326,6 +2343,39 @@ __device__ __forceinline__ void sched_loop_body(const MirrorView& m, const Batch
       }
     }
     publish_partials(par);
+    if (lane == 0) __hip_atomic_fetch_add(&s_e_done, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
+  };
+  // SPLIT, the post waves' half of a phase-1 round: the pod in `slot` on each of my nodes as if pod dprev were
+  // assumed there (what phase 1's post branch computes in the same lane).  It reads the cores and the two programs
+  // and writes only the *2 arrays, so it waits for nothing the as-is waves write.  s_e_done is bumped every round,
+  // also when there is nothing to prepare: the helper counts 2 * NW arrivals per round.
+  auto phase1_post = [&](int slot, const PodDesc* dprev) __attribute__((always_inline)) {
+    const uint8_t* base = s_blob[slot];
+    const PodDesc& d = *reinterpret_cast<const PodDesc*>(base);
+    if (dprev && post_ok(*dprev, d)) {
+      const PodFast pf = load_fast(base, d);
+      const int ts = t - kPost0 * 64, ws = wave - kPost0;  // my slot and evaluation wave
+#pragma unroll
+      for (int kk = 0; kk < kLoopMaxBlk; ++kk) {
+        if (kk < nk) {
+          const int i = (k0 + kk) * U + ts;
+          NodeEval ne2{1u, false, 0, 0, 0, 0};
+          if (i < m.n) {
+            NodeCore c2 = lds_core(s_core, kk, ts);
+            assume_core(c2, *dprev);
+            // (requests that match the previous pod's: the as-is wave's BalancedAllocation with the pod, same bits)
+            const int64_t wo2 = bal2(c2.rcpu, c2.acpu, c2.rmem, c2.amem);
+            ne2 = eval_core_fast<NOM>(m, c2, wo2, pf, base, d, i);
+            s_bwo2[kk][ts] = wo2;
+          }
+          const unsigned long long b2 = __ballot(ne2.st == 0);
+          if (lane == 0) s_ball2[kk][ws] = b2;
+          s_fx2[kk][ts] = ne2.fixed;
+          s_rt2[kk][ts] = (uint32_t)ne2.rt;
+          s_rn2[kk][ts] = (uint32_t)ne2.rna;
+        }
+      }
+    }
     if (lane == 0) __hip_atomic_fetch_add(&s_e_done, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
   };
   // phase 2 over the slots of evaluation waves [vlo, vhi) of every block of my range (the selection
@@ -2483,6 +2533,8 @@ __device__ __forceinline__ void sched_loop_body(const MirrorView& m, const Batch
   // rotation start from the ballots)
   const bool ahead = RING && spec_for == run0 && ((s_ring_ctl >> 11) & 1ull);
   if (t < U && !ahead) phase1(lv.first_pod + run0, run0 % 3, run0 & 1, nullptr);
+  if constexpr (SPLIT)
+    if (pst) phase1_post(run0 % 3, nullptr);  // nothing to prepare for a run's first pod: the round is counted
   __syncthreads();
   if (vt == U) {
     const PodDesc& d0 = *reinterpret_cast<const PodDesc*>(s_blob[run0 % 3]);
@@ -2678,7 +2730,7 @@ __device__ __forceinline__ void sched_loop_body(const MirrorView& m, const Batch
         const PodDesc& nd = *reinterpret_cast<const PodDesc*>(nb);
         cand_ok = cand >= 0 && post_ok(d, nd) ? 1u : 0u;
         while (__hip_atomic_load(&s_e_done, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) <
-               (uint32_t)(NW) * (uint32_t)(q + 2))
+               (uint32_t)(SPLIT ? 2 * NW : NW) * (uint32_t)(q + 2))
           __builtin_amdgcn_s_sleep(1);
         // Everything both variants read is loaded at once (independent LDS reads, one round trip), and
         // the candidate's replacement values are formed in registers: this runs between phase 1 of pod
@@ -2800,6 +2852,13 @@ __device__ __forceinline__ void sched_loop_body(const MirrorView& m, const Batch
         __hip_atomic_store(&s_ga_q, q, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
       }
 
+    } else if (SPLIT && pst) {
+      // ======== post-evaluation waves (SPLIT): pod q+1 on each node as if this pod were assumed there
+      if (more) {
+        phase1_post(bn, &d);
+        if (kSt && lv.wstamps && lane == 0)  // phase-1 end covers these waves too
+          atomicMax(&lv.wstamps[((size_t)q * G + w) * 8 + 6], __builtin_amdgcn_s_memrealtime());
+      }
     } else if (more) {
       // ======== evaluation waves: phase 1 of pod q+1 against the cores before this pod's assume.
       // Only the chosen node changes; its owner redoes it below.
@@ -2921,10 +2980,12 @@ __device__ __forceinline__ void sched_loop_body(const MirrorView& m, const Batch
 // by-value parameters to the body's references made the compiler copy them into registers up front (scratch spills)
 // NOM: the launch carries a nominee table (MirrorView::nom); launches without one -- the common case -- run the
 // instances compiled without the overlay
-template <int NW, bool RING, int MS = kMaxSweep, bool NOM = false>
-__global__ __launch_bounds__(NW * 64 + 128) void k_sched_loop(MirrorView m, BatchView b, LoopView lv) {
+// SPLIT: the instance with NW more waves for phase 1's post evaluation (kSplitThreads threads)
+constexpr int kSplitThreads = 2 * (2 * 64) + 128;
+template <int NW, bool RING, int MS = kMaxSweep, bool NOM = false, bool SPLIT = false>
+__global__ __launch_bounds__(NW * 64 + 128 + (SPLIT ? NW * 64 : 0)) void k_sched_loop(MirrorView m, BatchView b, LoopView lv) {
   const LoopGroupArg& a = *(const LoopGroupArg*)__builtin_amdgcn_kernarg_segment_ptr();
-  sched_loop_body<NW, RING, MS, false, NOM>(a.m, a.b, a.lv, 0);
+  sched_loop_body<NW, RING, MS, false, NOM, SPLIT>(a.m, a.b, a.lv, 0);
 }
 // In-process rank groups (localGroup: W contexts on one device): every rank's loop in ONE dispatch, block
 // r * G + w playing rank r's workgroup w with rank r's views.  Loops of separate dispatches on separate
@@ -5162,7 +5223,16 @@ hipError_t launch_sched_loop(const MirrorView& m, const BatchView& b, const Loop
       hipLaunchKernelGGL((k_sched_loop<2, true>), dim3(lv.nwg), dim3(2 * 64 + 128), 0, s, m, b, lv);
     else
       hipLaunchKernelGGL((k_sched_loop<4, true>), dim3(lv.nwg), dim3(kLoopThreads), 0, s, m, b, lv);
-  } else if (unit == 128 && lv.world * lv.nwg <= 64) {  // one sweep round (C2's 40 workgroups)
+  } else if (unit == 128 && lv.split_eval && lv.world == 1) {  // the split instances (unsharded batch runs)
+    const dim3 grid(lv.nwg), blk(kSplitThreads);
+    if (lv.nwg <= 64) {  // one sweep round (C2's 40 workgroups)
+      if (t0) hipExtLaunchKernelGGL((k_sched_loop<2, false, 1, false, true>), grid, blk, 0, s, t0, t1, 0, m, b, lv);
+      else hipLaunchKernelGGL((k_sched_loop<2, false, 1, false, true>), grid, blk, 0, s, m, b, lv);
+    } else {
+      if (t0) hipExtLaunchKernelGGL((k_sched_loop<2, false, kMaxSweep, false, true>), grid, blk, 0, s, t0, t1, 0, m, b, lv);
+      else hipLaunchKernelGGL((k_sched_loop<2, false, kMaxSweep, false, true>), grid, blk, 0, s, m, b, lv);
+    }
+  } else if (unit == 128 && lv.world * lv.nwg <= 64) {  // one sweep round
     if (t0)
       hipExtLaunchKernelGGL((k_sched_loop<2, false, 1>), dim3(lv.nwg), dim3(2 * 64 + 128), 0, s, t0, t1, 0, m, b, lv);
     else
@@ -5244,14 +5314,18 @@ hipError_t loop_occupancy(int (&occ)[4]) {
     const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ[i], ks[i].f, ks[i].threads, 0);
     if (e != hipSuccess) return e;
   }
-  // (k_sched_loop's instances with the nominee overlay use more registers: a grid must fit either)
-  const K kn[2] = {{reinterpret_cast<const void*>(&k_sched_loop<2, false, kMaxSweep, true>), 2 * 64 + 128},
-                   {reinterpret_cast<const void*>(&k_sched_loop<4, false, kMaxSweep, true>), kLoopThreads}};
-  for (int i = 0; i < 2; ++i) {
+  // (k_sched_loop's instances with the nominee overlay use more registers, its split instances have six waves:
+  // a grid must fit whichever is launched)
+  const K kn[4] = {{reinterpret_cast<const void*>(&k_sched_loop<2, false, kMaxSweep, true>), 2 * 64 + 128},
+                   {reinterpret_cast<const void*>(&k_sched_loop<4, false, kMaxSweep, true>), kLoopThreads},
+                   {reinterpret_cast<const void*>(&k_sched_loop<2, false, 1, false, true>), kSplitThreads},
+                   {reinterpret_cast<const void*>(&k_sched_loop<2, false, kMaxSweep, false, true>), kSplitThreads}};
+  for (int i = 0; i < 4; ++i) {
     int o = 0;
     const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&o, kn[i].f, kn[i].threads, 0);
     if (e != hipSuccess) return e;
-    occ[i] = o < occ[i] ? o : occ[i];
+    const int k = i < 2 ? i : 0;  // the split instances: 128-node units
+    occ[k] = o < occ[k] ? o : occ[k];
   }
   return hipSuccess;
 }
@@ -5271,7 +5345,9 @@ hipError_t warm_kernels() {
                       reinterpret_cast<const void*>(&k_sched_loop<2, false, kMaxSweep, true>),
                       reinterpret_cast<const void*>(&k_sched_loop<4, true, kMaxSweep, true>),
                       reinterpret_cast<const void*>(&k_sched_loop<2, true, kMaxSweep, true>),
-                      reinterpret_cast<const void*>(&k_sample_apply),        reinterpret_cast<const void*>(&k_sample_shard_a),
+                      reinterpret_cast<const void*>(&k_sched_loop<2, false, 1, false, true>),
+                      reinterpret_cast<const void*>(&k_sched_loop<2, false, kMaxSweep, false, true>),
+                      reinterpret_cast<const void*>(&k_sample_apply),       reinterpret_cast<const void*>(&k_sample_shard_a),
                       reinterpret_cast<const void*>(&k_sample_shard_b),        reinterpret_cast<const void*>(&k_node_update),
                       reinterpret_cast<const void*>(&k_node_dyn),           reinterpret_cast<const void*>(&k_agg_loop<false, false>),
                       reinterpret_cast<const void*>(&k_agg_loop<false, true>),

@@ -2457,6 +2457,8 @@ int Engine::run_batch(const std::vector<const PodSpec*>& pods, const std::vector
       lv.desc_bytes = (const uint32_t*)d_off.p + n;
       lv.give_up_at = c->cfg.debug_give_up_at;
       lv.wave_map = c->cfg.loop_wave_map;
+      // the split instance: unsharded 128-node-unit runs without a nominee table (launch_sched_loop)
+      lv.split_eval = c->cfg.loop_split_eval && unit == 128 && W == 1 && !comm && m.nom == nullptr ? 1 : 0;
       lv.wstamps = c->cfg.loop_stamps ? (unsigned long long*)d_stamps.p + (size_t)n * 8 + 64 + (size_t)i * GS * 8 : nullptr;
       // in-process ranks: every rank is past its allocations before any rank's first loop starts
       if ((runs.empty() || regate) && comm) htrace("gate", i);

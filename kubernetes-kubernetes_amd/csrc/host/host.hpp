@@ -229,7 +229,8 @@ struct Config {
   // of G; round 6, profiles/r06d_resident_ab.txt: C2's 40 workgroups 19.8 -> 14.8 us per call, DTS's 20 27.0 -> 25.3)
   int ring_relay_min = 2;
   int first_chunk = 32;         // pods in a pipelined batch's first chunk (the host work before the first launch)
-  int loop_wave_map = 0;        // k_sched_loop role-to-wave placement (kWaveMap in kernels.hip)
+  int loop_wave_map = 0;        // k_sched_loop role-to-wave placement (kWaveMap / kSplitWaveMap in kernels.hip)
+  bool loop_split_eval = true;  // k_sched_loop: phase 1's two evaluations on separate waves ("loopSplitEval")
   bool resident_ahead = true;   // resident loops: the next pod's phase 1 ahead of its doorbell (LoopView, AggView bit 7)
   int debug_give_up_at = -1;    // diagnostic: the persistent loops give up at this pod of a run
   int loop_wg = 0;              // k_sched_loop workgroups (0: min(node units, CUs, 128))

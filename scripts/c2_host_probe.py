@@ -46,6 +46,15 @@ if sys.argv[1:] == ["wavemap"]:
     for wm in (0, 1, 2):
         run({"loopWaveMap": wm, "loopStamps": True}, f"loopWaveMap {wm} stamps")
     sys.exit(0)
+if sys.argv[1:] == ["split"]:  # the unsplit instance against the split one under both role placements, interleaved
+    cfgs = [({"loopSplitEval": False}, "unsplit"), ({"loopWaveMap": 0}, "split map 0"), ({"loopWaveMap": 1}, "split map 1")]
+    for rep in range(3):
+        for cfg, label in cfgs:
+            run(cfg, label)
+    for cfg, label in cfgs:
+        print(f"==== stamps: {label}", file=sys.stderr, flush=True)
+        run(dict(cfg, loopStamps=True), f"{label} stamps")
+    sys.exit(0)
 if sys.argv[1:] != ["stamps"]:
     run({"loopTimingStride": 1}, "events on every loop launch")
     run({"loopTimingStride": 0}, "no loop events")
