@@ -319,7 +319,7 @@ void Cluster::intern_node(NodeRec& r) {
   r.alloc_cpu = r.alloc_mem = r.alloc_eph = r.alloc_pods = 0;
   r.scalar_alloc.clear();
   for (auto& a : r.spec.alloc) {
-    if (a.name == "cpu") r.alloc_cpu += a.milli;
+    if (a.name == "cpu") r.alloc_cpu += milli_value(a.milli);
     else if (a.name == "memory") r.alloc_mem += milli_ceil(a.milli);
     else if (a.name == "pods") r.alloc_pods += milli_ceil(a.milli);
     else if (a.name == "ephemeral-storage") r.alloc_eph += milli_ceil(a.milli);

@@ -464,10 +464,10 @@ int Engine::compile(const PodSpec& p, Mode mode, int plugin, bool assume, bool e
     for (auto& sp : specs) {
       ScoreRes r{};
       r.weight = sp.second;
-      int64_t m = 0;
+      Milli m = 0;
       for (auto& x : reqs)
         if (x.name == sp.first) m = x.milli;
-      r.pod_req = sp.first == "cpu" ? m : milli_ceil(m);
+      r.pod_req = sp.first == "cpu" ? milli_value(m) : milli_ceil(m);
       if (r.pod_req != 0) *best_effort = false;
       if (sp.first == "cpu") r.kind = RES_CPU;
       else if (sp.first == "memory") r.kind = RES_MEM;

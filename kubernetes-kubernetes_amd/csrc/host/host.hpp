@@ -32,14 +32,19 @@ namespace ksg {
 // ===================================================================================
 using StrMap = std::vector<std::pair<std::string, std::string>>;  // sorted by key
 
-struct ResAmount {  // v1.ResourceList entry, quantity in milli-units (Quantity.MilliValue())
+// Milli-units in 128 bits: Quantity.Value() is exact up to 2^63 - 1 whole units (memory in bytes), which
+// int64 milli-units cannot hold; sums of requests stay exact too.
+using Milli = __int128;
+constexpr Milli kMilliMax = (Milli)INT64_MAX * 1000;  // a parsed quantity's magnitude saturates here
+struct ResAmount {  // v1.ResourceList entry, quantity in milli-units
   std::string name;
-  int64_t milli;
+  Milli milli;
 };
 using ResVec = std::vector<ResAmount>;
 
-bool parse_quantity(const std::string& s, int64_t* milli);
-int64_t milli_ceil(int64_t m);  // Quantity.Value() from milli-units (rounds up)
+bool parse_quantity(const std::string& s, Milli* milli);
+int64_t milli_ceil(Milli m);   // Quantity.Value() from milli-units (rounds up), saturating at the int64 range
+int64_t milli_value(Milli m);  // Quantity.MilliValue() (cpu), saturating at the int64 range
 bool parse_go_int(const std::string& s, int64_t* v);  // strconv.ParseInt(s, 10, 64)
 bool parse_rfc3339(const std::string& s, int64_t* unix_ns);  // metav1.Time (RFC 3339, optional fraction)
 bool valid_label_key(const std::string& k);            // validation.IsQualifiedName

@@ -9,7 +9,7 @@ namespace ksg {
 // ---- resource.Quantity -> milli-units (apimachinery/pkg/api/resource/quantity.go) ------------
 // The value is held exactly as digits * 2^b2 * 10^e10 and scaled to milli with a
 // round-up (MilliValue / ScaledValue semantics).
-bool parse_quantity(const std::string& s, int64_t* milli) {
+bool parse_quantity(const std::string& s, Milli* milli) {
   const char* p = s.c_str();
   const char* e = p + s.size();
   int sign = 1;
@@ -63,19 +63,20 @@ bool parse_quantity(const std::string& s, int64_t* milli) {
   int scale = e10 - frac_digits + 3;
   for (; scale > 0; --scale) {
     v *= 10u;
-    if (v > cap) { *milli = sign > 0 ? LLONG_MAX : LLONG_MIN; return true; }
+    if (v > cap) { *milli = sign > 0 ? kMilliMax : -kMilliMax; return true; }
   }
   if (scale < 0) {
     unsigned __int128 d = 1;
     for (; scale < 0 && d < cap; ++scale) d *= 10u;
     v = sign > 0 ? (v + d - 1) / d : v / d;
   }
-  if (v > (unsigned __int128)LLONG_MAX) v = LLONG_MAX;
-  *milli = sign > 0 ? (int64_t)v : -(int64_t)v;
+  if (v > (unsigned __int128)kMilliMax) v = (unsigned __int128)kMilliMax;
+  *milli = sign > 0 ? (Milli)v : -(Milli)v;
   return true;
 }
 
-int64_t milli_ceil(int64_t m) { return m >= 0 ? m / 1000 + (m % 1000 ? 1 : 0) : m / 1000; }
+int64_t milli_value(Milli m) { return m > (Milli)INT64_MAX ? INT64_MAX : m < (Milli)INT64_MIN ? INT64_MIN : (int64_t)m; }
+int64_t milli_ceil(Milli m) { return milli_value(m >= 0 ? m / 1000 + (m % 1000 ? 1 : 0) : m / 1000); }
 
 bool parse_go_int(const std::string& s, int64_t* v) {
   if (s.empty()) return false;
@@ -148,7 +149,7 @@ static std::vector<std::string> str_list(const JDoc& d, const JVal* a) {
 static bool res_list(const JDoc& d, const JVal* o, ResVec* out, std::string* err) {
   bool ok = true;
   d.each(o, [&](const JVal& v) {
-    int64_t m;
+    Milli m;
     if (!ok) return;
     if (!parse_quantity(v.s, &m)) {
       *err = "invalid quantity " + v.key + "=" + v.s;
@@ -751,7 +752,7 @@ ResVec pod_requests(const PodSpec& p, const ResVec* non_missing, bool use_status
     const ResVec effr = eff ? effective_requests(p.resize_infeasible, p.pod_requests, p.pod_st_req, p.pod_st_alloc) : ResVec{};
     for (const auto& r : p.pod_requests)
       if (pod_level_supported(r.name)) {
-        int64_t v = r.milli;
+        Milli v = r.milli;
         if (eff) {
           auto e = std::find_if(effr.begin(), effr.end(), [&](const ResAmount& x) { return x.name == r.name; });
           v = e == effr.end() ? 0 : e->milli;
@@ -776,13 +777,13 @@ PodResources calc_resources(const PodSpec& p) {  // framework/types.go:1035-1076
   const ResVec non0 = nm.empty() ? requests : pod_requests(p, &nm, true);
   PodResources out;
   for (const auto& r : requests) {
-    if (r.name == "cpu") out.cpu += r.milli;
+    if (r.name == "cpu") out.cpu += milli_value(r.milli);
     else if (r.name == "memory") out.mem += milli_ceil(r.milli);
     else if (r.name == "ephemeral-storage") out.eph += milli_ceil(r.milli);
     else if (r.name != "pods" && scalar_resource(r.name)) out.scalar.push_back({r.name, milli_ceil(r.milli)});
   }
   for (const auto& r : non0) {
-    if (r.name == "cpu") out.nz_cpu = r.milli;
+    if (r.name == "cpu") out.nz_cpu = milli_value(r.milli);
     else if (r.name == "memory") out.nz_mem = milli_ceil(r.milli);
   }
   return out;
@@ -791,7 +792,7 @@ PodResources calc_resources(const PodSpec& p) {  // framework/types.go:1035-1076
 PodResources calc_fit_request(const PodSpec& p) {  // fit.go:317-325 (SetMaxResource over PodRequests)
   PodResources out;
   for (const auto& r : pod_requests(p, nullptr, false)) {
-    if (r.name == "cpu") out.cpu += r.milli;
+    if (r.name == "cpu") out.cpu += milli_value(r.milli);
     else if (r.name == "memory") out.mem += milli_ceil(r.milli);
     else if (r.name == "ephemeral-storage") out.eph += milli_ceil(r.milli);
     else if (r.name != "pods" && scalar_resource(r.name)) out.scalar.push_back({r.name, milli_ceil(r.milli)});

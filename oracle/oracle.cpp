@@ -357,7 +357,7 @@ static bool check_conflict(const HostPorts& h, std::string ip, std::string proto
 static Resource node_allocatable(const Node& n) {  // NewResource(node.Status.Allocatable), types.go:1263-1291
   Resource r;
   for (auto& kv : n.allocatable) {
-    if (kv.first == "cpu") r.milliCPU += kv.second;
+    if (kv.first == "cpu") r.milliCPU += milli_value(kv.second);
     else if (kv.first == "memory") r.memory += milli_to_value(kv.second);
     else if (kv.first == "pods") r.allowedPods += milli_to_value(kv.second);
     else if (kv.first == "ephemeral-storage") r.ephemeral += milli_to_value(kv.second);
@@ -965,7 +965,7 @@ static Status run_prefilter_plugin(Cycle& cy, int p, bool* skip, std::vector<std
       Resource r;  // SetMaxResource (types.go:1325-1344)
       for (auto& kv : reqs) {
         if (kv.first == "memory") r.memory = std::max(r.memory, milli_to_value(kv.second));
-        else if (kv.first == "cpu") r.milliCPU = std::max(r.milliCPU, kv.second);
+        else if (kv.first == "cpu") r.milliCPU = std::max(r.milliCPU, milli_value(kv.second));
         else if (kv.first == "ephemeral-storage") r.ephemeral = std::max(r.ephemeral, milli_to_value(kv.second));
         else if (is_scalar_resource_name(kv.first)) r.scalar[kv.first] = std::max(r.scalar[kv.first], milli_to_value(kv.second));
       }
@@ -1178,8 +1178,8 @@ static int64_t pod_resource_request(const Pod& pod, const std::string& name, boo
   if (!useRequested) { nonMissing["cpu"] = 100; nonMissing["memory"] = 200LL * 1024 * 1024 * 1000; }
   ResList reqs = pod_requests(pod, useRequested ? nullptr : &nonMissing, true);  // UseStatusResources
   auto it = reqs.find(name);
-  int64_t m = it == reqs.end() ? 0 : it->second;
-  return name == "cpu" ? m : milli_to_value(m);
+  const Milli m = it == reqs.end() ? 0 : it->second;
+  return name == "cpu" ? milli_value(m) : milli_to_value(m);
 }
 
 // resource_allocation.go:167-232
@@ -1568,7 +1568,7 @@ static bool sign_pod(const ksgo_ctx* c, const Pod& p, std::string* sig) {
     bool scalar = false;
     for (auto& kv : pod_requests(p, nullptr, false)) {
       if (kv.first == "memory") r.memory = std::max(r.memory, milli_to_value(kv.second));
-      else if (kv.first == "cpu") r.milliCPU = std::max(r.milliCPU, kv.second);
+      else if (kv.first == "cpu") r.milliCPU = std::max(r.milliCPU, milli_value(kv.second));
       else if (kv.first == "ephemeral-storage") r.ephemeral = std::max(r.ephemeral, milli_to_value(kv.second));
       else if (kv.first == "pods") pods = std::max(pods, milli_to_value(kv.second));
       else if (is_scalar_resource_name(kv.first)) {
@@ -2760,7 +2760,7 @@ int ksgo_debug_pod_resources(const char* json, size_t len, int64_t* out, int32_t
   const PodResource r = calculate_resource(p);
   int64_t fit[3] = {0, 0, 0};
   for (auto& kv : pod_requests(p, nullptr, false)) {
-    if (kv.first == "cpu") fit[0] = kv.second;
+    if (kv.first == "cpu") fit[0] = milli_value(kv.second);
     else if (kv.first == "memory") fit[1] = milli_to_value(kv.second);
     else if (kv.first == "ephemeral-storage") fit[2] = milli_to_value(kv.second);
   }

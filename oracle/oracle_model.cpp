@@ -13,7 +13,7 @@ namespace oracle {
 // resource.Quantity  (apimachinery/pkg/api/resource/quantity.go: parseQuantityString,
 // suffix tables in suffix.go; MilliValue = ScaledValue(-3) rounds up)
 // ============================================================================
-bool parse_quantity_milli(const std::string& s, int64_t* milli) {
+bool parse_quantity_milli(const std::string& s, Milli* milli) {
   size_t i = 0, n = s.size();
   bool neg = false;
   if (i < n && (s[i] == '+' || s[i] == '-')) neg = s[i++] == '-';
@@ -60,17 +60,17 @@ bool parse_quantity_milli(const std::string& s, int64_t* milli) {
   // value*1000 = mant * 2^p2 * 10^(p10 - frac + 3), rounded up
   unsigned __int128 v = mant;
   const unsigned __int128 lim = (unsigned __int128)1 << 120;
-  for (int k = 0; k < p2; ++k) { v <<= 1; if (v > lim) { *milli = neg ? LLONG_MIN : LLONG_MAX; return true; } }
+  for (int k = 0; k < p2; ++k) { v <<= 1; if (v > lim) { *milli = neg ? -kMilliMax : kMilliMax; return true; } }
   int e10 = p10 - frac + 3;
   if (e10 >= 0) {
-    for (int k = 0; k < e10; ++k) { v *= 10; if (v > lim) { *milli = neg ? LLONG_MIN : LLONG_MAX; return true; } }
+    for (int k = 0; k < e10; ++k) { v *= 10; if (v > lim) { *milli = neg ? -kMilliMax : kMilliMax; return true; } }
   } else {
     unsigned __int128 den = 1;
     for (int k = 0; k < -e10 && den < lim; ++k) den *= 10;
     v = neg ? v / den : (v + den - 1) / den;  // ceil toward +inf
   }
-  if (v > (unsigned __int128)LLONG_MAX) v = (unsigned __int128)LLONG_MAX;
-  *milli = neg ? -(int64_t)v : (int64_t)v;
+  if (v > (unsigned __int128)kMilliMax) v = (unsigned __int128)kMilliMax;
+  *milli = neg ? -(Milli)v : (Milli)v;
   return true;
 }
 
@@ -244,7 +244,7 @@ static std::vector<std::string> decode_strs(const mj::Value* v) {
 static bool decode_reslist(const mj::Value* v, ResList* out, std::string* err) {
   if (!v || !v->is_obj()) return true;
   for (auto& kv : v->obj) {
-    int64_t m = 0;
+    Milli m = 0;
     std::string txt = kv.second.kind == mj::Value::Number ? kv.second.s : kv.second.s;
     if (!parse_quantity_milli(txt, &m)) {
       *err = "bad quantity " + kv.first + "=" + txt;
@@ -860,13 +860,13 @@ PodResource calculate_resource(const Pod& p) {  // framework/types.go:1035-1076 
   PodResource r;
   // Resource.Add (types.go:1270-1291): cpu -> MilliValue, others -> Value
   for (auto& kv : requests) {
-    if (kv.first == "cpu") r.res.milliCPU += kv.second;
+    if (kv.first == "cpu") r.res.milliCPU += milli_value(kv.second);
     else if (kv.first == "memory") r.res.memory += milli_to_value(kv.second);
     else if (kv.first == "pods") r.res.allowedPods += milli_to_value(kv.second);
     else if (kv.first == "ephemeral-storage") r.res.ephemeral += milli_to_value(kv.second);
     else if (is_scalar_resource_name(kv.first)) r.res.scalar[kv.first] += milli_to_value(kv.second);
   }
-  r.non0CPU = non0.count("cpu") ? non0["cpu"] : 0;
+  r.non0CPU = non0.count("cpu") ? milli_value(non0["cpu"]) : 0;
   r.non0Mem = non0.count("memory") ? milli_to_value(non0["memory"]) : 0;
   return r;
 }

@@ -19,14 +19,21 @@ namespace oracle {
 using Labels = std::map<std::string, std::string>;
 // v1.ResourceList with every quantity held as Quantity.MilliValue() (exact for
 // quantities with at most milli precision, which covers every scheduler input we use).
-using ResList = std::map<std::string, int64_t>;
+// Milli-units in 128 bits: Quantity.Value() is exact up to 2^63 - 1 whole units (memory in bytes), which
+// int64 milli-units cannot hold; sums of requests stay exact too.
+using Milli = __int128;
+using ResList = std::map<std::string, Milli>;
+constexpr Milli kMilliMax = (Milli)INT64_MAX * 1000;  // a parsed quantity's magnitude saturates here
 
 // ---- resource.Quantity -------------------------------------------------------------
 // staging/src/k8s.io/apimachinery/pkg/api/resource/quantity.go (ParseQuantity,
 // MilliValue/Value round up = ceil for the non-negative values requests carry).
-bool parse_quantity_milli(const std::string& s, int64_t* milli);
-// (ceil for m >= 0 without the m + 999 overflow at the int64 edge; truncation toward zero below 0)
-inline int64_t milli_to_value(int64_t m) { return m >= 0 ? m / 1000 + (m % 1000 ? 1 : 0) : m / 1000; }
+bool parse_quantity_milli(const std::string& s, Milli* milli);
+inline int64_t milli_clamp(Milli v) { return v > (Milli)INT64_MAX ? INT64_MAX : v < (Milli)INT64_MIN ? INT64_MIN : (int64_t)v; }
+// Quantity.Value(): ceil for m >= 0, truncation toward zero below 0; saturates at the int64 range
+inline int64_t milli_to_value(Milli m) { return milli_clamp(m >= 0 ? m / 1000 + (m % 1000 ? 1 : 0) : m / 1000); }
+// Quantity.MilliValue() (cpu): saturates at the int64 range
+inline int64_t milli_value(Milli m) { return milli_clamp(m); }
 
 // ---- labels.Selector -----------------------------------------------------------------
 enum class Op { In, NotIn, Exists, DoesNotExist, Gt, Lt, Equals };

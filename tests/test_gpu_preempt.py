@@ -425,3 +425,117 @@ def test_preempt_beyond_register_store(native, seed):
         r, _ = compare(dev, orc, pod, args)
         found += r.status == 0
     assert found > 0
+
+
+# ---- k_preempt_pick's block edges ---------------------------------------------------------------------------
+# The pick walks the potential nodes in blocks of 1024 threads, carries the running candidate counts from block
+# to block, finds the cut with an atomicMin and leaves the block loop once it is known; ties go to the earliest
+# candidate in rotated order.  2500 identical full nodes (every one a potential node: three blocks), of which
+# only chosen ones hold pods of a lower priority than the preemptor, put the cut, the wrap of the rotation and
+# the tied candidates where the blocks meet.
+PICK_P = 2500
+PICK_NOW = 1704153600 * 10 ** 9
+
+
+def pick_cluster(kind):
+    """kind "sparse": candidates on every 37th node only (68 of them, one victim each, all identical: the first
+    50 labelled app=guard, the rest app=free); "sparse-best": the same with a lower-priority victim on node 740;
+    "dense": every node a candidate (one or two victims)."""
+    nodes, existing = [], []
+    for i in range(PICK_P):
+        alloc = {"cpu": "1000m", "memory": str(1024 ** 3), "pods": "110"}
+        nodes.append({"apiVersion": "v1", "kind": "Node", "metadata": {"name": f"n{i:05d}", "labels": {}},
+                      "spec": {}, "status": {"allocatable": alloc, "capacity": alloc}})
+        cand = kind == "dense" or i % 37 == 0
+        two = i % 2 == 1 if kind == "dense" else (i % 37) % 2 == 1
+        prio = 0 if cand else 1000
+        if kind == "sparse-best" and i == 740:
+            prio = -10
+        for k in range(2 if two else 1):
+            existing.append({"apiVersion": "v1", "kind": "Pod",
+                             "metadata": {"name": f"b-{i}-{k}", "namespace": "default", "uid": f"b-{i}-{k}",
+                                          "labels": {"app": "guard" if i // 37 < 50 else "free"}},
+                             "spec": {"nodeName": f"n{i:05d}", "priority": prio,
+                                      "containers": [{"name": "c", "image": "i", "resources": {"requests": {
+                                          "cpu": "500m" if two else "1000m", "memory": str(64 * 1024 ** 2)}}}]},
+                             "status": {"startTime": "2024-01-01T00:00:00Z"}})
+    return nodes, existing
+
+
+_pick_pairs = {}
+
+
+def pick_pair(native, kind):
+    """(device, oracle) contexts of one cluster, built once: the queries below change nothing."""
+    if kind not in _pick_pairs:
+        nodes, existing = pick_cluster(kind)
+        _pick_pairs[kind] = (build(native, nodes, existing), build(oracle, nodes, existing))
+    return _pick_pairs[kind]
+
+
+def pick_query(native, kind, offset, absn, pdbs=(), ncand=None, selected=None):
+    dev, orc = pick_pair(native, kind)
+    pod = {"apiVersion": "v1", "kind": "Pod", "metadata": {"name": "hi", "namespace": "default", "uid": "hi"},
+           "spec": {"priority": 100, "containers": [{"name": "c", "image": "i", "resources": {"requests": {
+               "cpu": "600m", "memory": str(64 * 1024 ** 2)}}}]}, "status": {}}
+    r, d = compare(dev, orc, pod, {"offset": offset, "now": PICK_NOW, "pdbs": list(pdbs),
+                                   "minCandidateNodesPercentage": 0, "minCandidateNodesAbsolute": absn})
+    assert r.status == 0 and r.num_potential == PICK_P, r.as_tuple()
+    assert r.num_candidates == ncand, r.as_tuple()
+    if selected is not None:
+        assert d["selected"] == f"n{selected:05d}", d["selected"]
+    return r, d
+
+
+def guard_pdb(apps):
+    return [{"metadata": {"namespace": "default"},
+             "spec": {"selector": {"matchExpressions": [{"key": "app", "operator": "In", "values": apps}]}},
+             "status": {"disruptionsAllowed": 0}}]
+
+
+@pytest.mark.parametrize("absn", [40, 60])
+def test_pick_cut_in_a_later_block(native, absn):
+    """The 40th candidate from offset 0 is node 39 * 37 = 1443 (the second block), the 60th node 2183 (the
+    third): the running counts of the earlier blocks decide the cut."""
+    pick_query(native, "sparse", 0, absn, ncand=absn, selected=0)
+
+
+@pytest.mark.parametrize("absn", [1024, 1025])
+def test_pick_cut_on_the_block_boundary(native, absn):
+    """Every node a candidate: the cut is rotated position 1023 (the first block's last thread) and 1024 (the
+    second block's first)."""
+    pick_query(native, "dense", 0, absn, ncand=absn)
+    pick_query(native, "dense", PICK_P - 500, absn, ncand=absn)
+
+
+def test_pick_no_cut_beyond_one_block(native):
+    """68 candidates, numCandidates 100: no cut, every block is walked."""
+    pick_query(native, "sparse", 0, 100, ncand=68, selected=0)
+    pick_query(native, "sparse", PICK_P - 500, 100, ncand=68, selected=2035)
+
+
+def test_pick_only_violating_candidates(native):
+    """A PodDisruptionBudget with no disruptions allowed over every victim: no non-violating candidate, so no
+    cut; the violating list is capped at numCandidates."""
+    pick_query(native, "sparse", 0, 40, pdbs=guard_pdb(["guard", "free"]), ncand=40, selected=0)
+    pick_query(native, "sparse", 3, 100, pdbs=guard_pdb(["guard", "free"]), ncand=68, selected=37)
+
+
+def test_pick_first_non_violating_after_full_violating_list(native):
+    """The first 50 candidates violate the budget, numCandidates is 40: the violating list is full at the 40th,
+    the cut is the 51st candidate (node 1850, the second block), the first non-violating one -- which wins."""
+    pick_query(native, "sparse", 0, 40, pdbs=guard_pdb(["guard"]), ncand=41, selected=1850)
+
+
+@pytest.mark.parametrize("offset", [0, PICK_P - 1, PICK_P - 500, 10 * PICK_P + 3])
+def test_pick_offsets_and_the_wrap(native, offset):
+    """Node 740's victim has the lowest priority: the best candidate.  From offset P - 500 the rotation wraps
+    inside the first block and node 740 comes after the wrap, in the second block."""
+    pick_query(native, "sparse-best", offset, 40, ncand=40, selected=740)
+
+
+@pytest.mark.parametrize("offset,first", [(0, 0), (PICK_P - 500, 2035), (1100, 1110)])
+def test_pick_full_ties_across_blocks(native, offset, first):
+    """All candidates identical (victims, priorities, start times): the earliest in rotated order wins, whichever
+    block of nodes it sits in, over 60 candidates spread across three blocks of positions."""
+    pick_query(native, "sparse", offset, 60, ncand=60, selected=first)
