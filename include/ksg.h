@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define KSG_ABI_VERSION 2 /* 2: ksg_eval_out.normalized_scores */
+#define KSG_ABI_VERSION 3 /* 2: ksg_eval_out.normalized_scores; 3: ksg_diagnosis, ksg_schedule_*_diag */
 
 /* ---- return codes of the ABI functions ------------------------------------------ */
 #define KSG_OK 0
@@ -87,6 +87,7 @@ extern "C" {
 #define KSG_R_IPA_ANTI_AFFINITY (1u << 14)   /* "node(s) didn't match pod anti-affinity rules" */
 #define KSG_R_IPA_EXISTING_ANTI (1u << 15)   /* "node(s) didn't satisfy existing pods anti-affinity rules" */
 #define KSG_R_PREFILTER (1u << 16)           /* node rejected by a PreFilter status / PreFilterResult */
+#define KSG_NUM_REASONS 17                   /* KSG_R_* bits 0..16 */
 
 typedef struct ksg_ctx ksg_ctx;
 
@@ -186,6 +187,43 @@ int ksg_schedule_one(ksg_ctx *ctx, int32_t handle, uint32_t flags, ksg_result *r
  * 0..i-1 (KSG_FLAG_ASSUME).  The whole batch runs device-resident. */
 int ksg_schedule_batch(ksg_ctx *ctx, const int32_t *handles, int32_t n, uint32_t flags,
                        ksg_result *results);
+
+/* ---- the FitError of a cycle, reduced on the device (ABI 3) ------------------------
+ * What handleSchedulingFailure needs of an unschedulable pod (schedule_one.go:842-848, framework/types.go:
+ * 1082-1180) without an N-sized copy: Diagnosis.UnschedulablePlugins (the queueing hints), the reason
+ * histogram of FitError.Error() ("0/N nodes are available: 3 Insufficient cpu, ...") and the split between
+ * Unschedulable and UnschedulableAndUnresolvable nodes (preemption).
+ * By definition a ksg_diagnosis is the reduction of the arrays ksg_eval_out would have held for the pod's
+ * own cycle -- in a batch, with the assumes of pods 0..i-1 applied and none later -- over the nodes whose
+ * node_code is non-zero:
+ *   - a status may carry several reason bits: a NodeResourcesFit failure on cpu and memory counts in both bins
+ *     (so the reason bins may sum to more than failed_nodes);
+ *   - a node whose status names no plugin (ksg_eval_out.node_plugin 255 with a non-zero code: a node outside a
+ *     PreFilterResult) counts in failed_nodes, in unresolvable_nodes by its code and in the KSG_R_PREFILTER bin;
+ *     it sets no bit of unschedulable_plugins and is in no plugin_nodes bin.  A PreFilter rejection gives every
+ *     node the rejecting plugin's status (prefilter_plugin): num_nodes nodes in that plugin's bin and in the
+ *     KSG_R_PREFILTER bin, as the evaluation output shows them;
+ *   - a node that failed alone first (the pod's own nominated node, an OpportunisticBatching hint) counts once,
+ *     as it appears once in the evaluation output;
+ *   - a cycle whose ksg_result.status is not Unschedulable / UnschedulableAndUnresolvable has every counter 0
+ *     (num_nodes, prefilter_code and prefilter_plugin are still filled).
+ * "Insufficient <extended resource>" is one bin for every extended resource (KSG_R_INSUFFICIENT_SCALAR). */
+typedef struct ksg_diagnosis {
+  int32_t num_nodes;              /* N of "0/N nodes are available": snapshot nodes of the cycle */
+  int32_t failed_nodes;           /* nodes in NodeToStatus with a non-success Filter status */
+  int32_t unresolvable_nodes;     /* of those, code UnschedulableAndUnresolvable */
+  uint32_t unschedulable_plugins; /* bit p: plugin p is the failing plugin of >= 1 rejected node
+                                     (Diagnosis.AddPluginStatus -> UnschedulablePlugins) */
+  int32_t prefilter_code, prefilter_plugin; /* as in ksg_eval_out */
+  int32_t plugin_nodes[KSG_NUM_PLUGINS];    /* nodes whose first failing plugin is p */
+  int32_t reason_nodes[KSG_NUM_REASONS];    /* nodes whose status carries reason bit r: FitError.Error()'s histogram */
+} ksg_diagnosis;
+/* ksg_schedule_one / ksg_schedule_batch with the diagnosis of every cycle (diags[n]); results, assumes and every
+ * side effect are those of the undiagnosed calls.  KSG_ENOTSUP on a node-sharded context. */
+int ksg_schedule_one_diag(ksg_ctx *ctx, int32_t handle, uint32_t flags, ksg_result *result, ksg_eval_out *eval /* may be NULL */,
+                          ksg_diagnosis *diag);
+int ksg_schedule_batch_diag(ksg_ctx *ctx, const int32_t *handles, int32_t n, uint32_t flags, ksg_result *results,
+                            ksg_diagnosis *diags /* [n] */);
 /* Cache.ForgetPod (cache.go:412) of an assumed pod -- unreserveAndForget (schedule_one.go:358) */
 int ksg_forget(ksg_ctx *ctx, int32_t handle);
 

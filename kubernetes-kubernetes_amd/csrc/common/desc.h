@@ -181,6 +181,8 @@ enum DescFlags : uint32_t {
   DF_NOMINATED = 1u << 24,         // status.nominatedNodeName names a snapshot node (nominated_node): k_nominated
                                    // runs that node's filters alone first (evaluateNominatedNode, schedule_one.go:
                                    // 657-669,714-745); feasible: the pod goes there, else the full pass follows
+  DF_DIAG = 1u << 25,              // a diagnosed call (ksg_schedule_*_diag): the node pass stores the status word as
+                                   // DF_EVAL_OUT does (not the score vectors) and k_diag_reduce follows k_select
 };
 // a pod the per-pod path may place before its full evaluation (PodStats::ob_done: 1 hint, 2 nominated node)
 constexpr uint32_t DF_EARLY = DF_OB | DF_NOMINATED;
@@ -501,6 +503,24 @@ struct BatchView {
   ObEnt* ob_heap;         // [cap] its sorted nodes (heap order)
 };
 
+// ---- FitError diagnosis rows ---------------------------------------------------
+// One row per pod of a diagnosed call: 32 int32 words, one 128-byte line.  The host zeroes the rows per
+// call, kernels only add to them (diag_accumulate: one relaxed agent-scope add per non-zero bin per
+// workgroup), and they come back with the results.  A bin counts the nodes of the pod's own cycle whose
+// Filter status is non-success (DG_FAILED), of those the UnschedulableAndUnresolvable ones (DG_UNRES), the
+// nodes per first failing plugin (plugin nibble 15 -- a PreFilterResult exclusion or a PreFilter rejection --
+// is in no plugin bin) and the nodes per KSG_R_* reason bit (a status may carry several).
+constexpr int kDiagWords = 32;
+constexpr int kNumReasons = 17;  // KSG_R_* bits 0..16
+enum DiagWord : int {
+  DG_FAILED = 0,
+  DG_UNRES = 1,
+  DG_PLUGIN = 2,                       // [kNumPlugins]
+  DG_REASON = DG_PLUGIN + kNumPlugins, // [kNumReasons]
+  DG_BINS = DG_REASON + kNumReasons,   // 29 bins; words 29..31 spare
+};
+static_assert(DG_BINS <= kDiagWords, "a diagnosis row is one 128-byte line");
+
 // ---- node-sharded evaluation ----------------------------------------------------
 // Every rank holds the whole mirror (replicated by the informer feed) and evaluates the nodes of
 // its contiguous block range.  Per pod, fixed-layout uint64 vectors are all-reduced with MAX:
@@ -642,6 +662,9 @@ struct LoopView {
   // resident mode with many workgroups: workgroup 0 alone polls the host's ctl and relays the word through
   // device memory (relay[0]), where the others poll (nullptr: every workgroup polls the host)
   unsigned long long* relay;
+  // a diagnosed batch run (ksg_schedule_batch_diag): the batch's diagnosis rows, [batch pods][kDiagWords] -- the
+  // DIAG instances add a pod's per-node statuses to its row where its cycle ends without a feasible node
+  int32_t* diag;
 };
 // exchange granules per participant per pod: A0 {count, count before nextStartNodeIndex},
 // A1 {max raw TT + 1, max raw NA + 1}, B {packed key < 2^48}, B_node (sharded only) -- four words used, the row

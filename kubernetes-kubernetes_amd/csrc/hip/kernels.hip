@@ -566,7 +566,7 @@ __device__ __forceinline__ NodeEval eval_node(const MirrorView& m, const BatchVi
                 : 0u;
       st = f;
     }
-    if (kStore && eval) b.status[i] = st;
+    if (kStore && (d.flags & (DF_EVAL_OUT | DF_DIAG))) b.status[i] = st;  // (DF_DIAG: k_diag_reduce reads it)
   }
   DIAG_STAMP(2);
   r.st = valid ? st : 1u;
@@ -1322,7 +1322,7 @@ __global__ void k_nominated(MirrorView m, BatchView b, int pod) {
   const uint32_t st = run_filters(m, load_core(m, nn), base, d, nn, &rt, ArenaTopo{ps, b.arena}, 0);
   if (st != 0) {
     ps->nom_failed = (uint32_t)nn + 1u;
-    if (d.flags & DF_EVAL_OUT) b.status[nn] = st;
+    if (d.flags & (DF_EVAL_OUT | DF_DIAG)) b.status[nn] = st;
     return;
   }
   if (d.flags & DF_ROTDEV) {
@@ -1333,6 +1333,71 @@ __global__ void k_nominated(MirrorView m, BatchView b, int pod) {
   b.results[pod].hinted = 2u;
   b.results[pod].evaluated = 1;  // EvaluatedNodes = 1 + diagnosis.NodeToStatus.Len() (no failure yet)
   ps->ob_done = 2u;
+}
+
+// ---- FitError diagnosis ------------------------------------------------------------------------
+// diag_accumulate: every wave that holds nodes of the pod brings one packed Filter status per lane (valid: the lane
+// has a node) and the workgroup adds its counts to the pod's row (desc.h DiagWord).  Per wave one ballot + popcount
+// per bin (29; lane r keeps bin r, over as many diag_count calls as the wave has node blocks); the waves meet in LDS
+// (DiagLds: LDS adds, then an arrival count), and the last wave to arrive does one relaxed agent-scope add per
+// non-zero bin and leaves the LDS words zero again.  No barrier: the caller zeroes the DiagLds once, behind a barrier,
+// and separates two uses by one.  The row is only ever added to (the host zeroed it).
+struct DiagLds {
+  uint32_t bin[DG_BINS];
+  uint32_t arrive;
+};
+__device__ __forceinline__ uint32_t diag_count(uint32_t st, bool valid, uint32_t mine) {
+  const int lane = threadIdx.x & 63;
+  const uint32_t code = status_code(st), plugin = status_plugin(st), reasons = status_reasons(st);
+  const bool fail = valid && code != 0u;
+  const unsigned long long bf = __ballot(fail);
+  if (bf == 0ull) return mine;  // wave-uniform
+  // (every ballot outside the lane test: all lanes of the wave take part in it)
+  const uint32_t nu = (uint32_t)__popcll(__ballot(fail && code == (uint32_t)C_UU));
+  mine += lane == DG_FAILED ? (uint32_t)__popcll(bf) : 0u;
+  mine += lane == DG_UNRES ? nu : 0u;
+#pragma unroll
+  for (int p = 0; p < kNumPlugins; ++p) {
+    const uint32_t c = (uint32_t)__popcll(__ballot(fail && plugin == (uint32_t)p));
+    mine += lane == DG_PLUGIN + p ? c : 0u;
+  }
+#pragma unroll
+  for (int r = 0; r < kNumReasons; ++r) {
+    const uint32_t c = (uint32_t)__popcll(__ballot(fail && ((reasons >> r) & 1u)));
+    mine += lane == DG_REASON + r ? c : 0u;
+  }
+  return mine;
+}
+__device__ __forceinline__ void diag_flush(uint32_t mine, int32_t* row, DiagLds& L, uint32_t nwaves) {
+  const int lane = threadIdx.x & 63;
+  if (lane < DG_BINS && mine) atomicAdd(&L.bin[lane], mine);
+  uint32_t last = 0;
+  if (lane == 0)  // (release: this wave's LDS adds above; acquire: the other waves', for the reads below)
+    last = __hip_atomic_fetch_add(&L.arrive, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_WORKGROUP) == nwaves - 1u ? 1u : 0u;
+  if (!__builtin_amdgcn_readfirstlane(last)) return;
+  if (lane < DG_BINS) {
+    const uint32_t v = __hip_atomic_load(&L.bin[lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    L.bin[lane] = 0u;
+    if (v) (void)__hip_atomic_fetch_add(row + lane, (int32_t)v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+  if (lane == 0) L.arrive = 0u;
+}
+__device__ __forceinline__ void diag_accumulate(uint32_t st, bool valid, int32_t* row, DiagLds& L, uint32_t nwaves) {
+  diag_flush(diag_count(st, valid, 0u), row, L, nwaves);
+}
+
+// k_diag_reduce (node blocks, behind k_select on the stream): the launch path's reduction of the status words the
+// pod's node pass stored (DF_DIAG) into its row.  The pod's outcome is read on the device: anything but a FitError
+// (no feasible node) returns at once and leaves the row zero.
+__global__ __launch_bounds__(kBlock) void k_diag_reduce(MirrorView m, BatchView b, int pod, int32_t* rows) {
+  __shared__ DiagLds s_dg;
+  const DevResult& r = b.results[pod];
+  if (r.feasible != 0 || (r.status != (int32_t)C_UNSCHED && r.status != (int32_t)C_UU)) return;  // workgroup-uniform
+  if (threadIdx.x <= DG_BINS) reinterpret_cast<uint32_t*>(&s_dg)[threadIdx.x] = 0u;
+  __syncthreads();
+  const int i = (int)blockIdx.x * kBlock + (int)threadIdx.x;
+  const bool valid = i < m.n;
+  diag_accumulate(valid ? b.status[i] : 0u, valid, rows + (size_t)pod * kDiagWords, s_dg, kBlock / 64);
 }
 
 // k_ob_store (one workgroup, after k_select): StoreScheduleResults (batch.go:98-158) for a signed pod whose
@@ -2140,9 +2205,12 @@ __constant__ int8_t kSplitWaveMap[2][6] = {{0, 1, 2, 3, 4, 5}, {4, 5, 0, 1, 2, 3
 // (the body of k_sched_loop and k_sched_loop_group: w = the workgroup this block plays in its rank)
 // (GRP: the group instance takes w from its block index; the others read blockIdx.x itself, as before the group
 // instance existed -- their register allocation is that sensitive)
-template <int NW, bool RING, int MS, bool GRP, bool NOM, bool SPLIT = false>
+// DIAG: a diagnosed batch run (LoopView::diag): where a pod's cycle ends without a feasible node, the evaluation
+// waves evaluate it once more and add the statuses to its row; the other instances are untouched
+template <int NW, bool RING, int MS, bool GRP, bool NOM, bool SPLIT = false, bool DIAG = false>
 __device__ __forceinline__ void sched_loop_body(const MirrorView& m, const BatchView& b, const LoopView& lv, const int w_grp) {
   static_assert(!SPLIT || (NW == 2 && !RING && !GRP && !NOM), "the split instance: unsharded 128-node-unit batch runs");
+  static_assert(!DIAG || (!RING && !GRP), "the diagnosing instances: unsharded batch runs");
   constexpr int U = NW * 64;                  // nodes per unit: one per evaluation-wave lane
   // NW evaluation waves, one selection wave, one helper wave (SPLIT: and NW post-evaluation waves)
   constexpr int kLoopThreads = U + 128 + (SPLIT ? U : 0);
@@ -2177,6 +2245,7 @@ __device__ __forceinline__ void sched_loop_body(const MirrorView& m, const Batch
   // percentageOfNodesToScore (DF_ROTDEV): s_rot[p & 1] = pod p's rotation start (nextStartNodeIndex),
   // s_proc = the decided pod's processedNodes (schedule_one.go:686-687, 809-824)
   __shared__ uint32_t s_rot[2], s_proc;
+  __shared__ DiagLds s_dg;  // DIAG: the evaluation waves' meeting point (diag_flush)
   const int w = GRP ? w_grp : (int)blockIdx.x, G = lv.nwg;
   if constexpr (!RING) loop_entry_record(lv.fail, w);  // (the resident instance is never sharded)
   const int gid = lv.rank * G + w, P = lv.world * G;  // my participant index, participants (rank-major)
@@ -2473,6 +2542,8 @@ __device__ __forceinline__ void sched_loop_body(const MirrorView& m, const Batch
     s_ga_q = -1;
     s_e_done = 0;
   }
+  if constexpr (DIAG)
+    if (threadIdx.x <= DG_BINS) reinterpret_cast<uint32_t*>(&s_dg)[threadIdx.x] = 0u;
   __syncthreads();
   // A batch launch is one run of pods [0, npods).  Resident mode (lv.ring): every pod is a run of its
   // own, started when the host posts it; the pod index q (granules, stamps, results) keeps counting.
@@ -2886,6 +2957,29 @@ __device__ __forceinline__ void sched_loop_body(const MirrorView& m, const Batch
             commit_result(m, b, base, d, rot_stats(pod, par), pod, F, -1, s_best, nullptr, s_ipa);
             if constexpr (RING) ring_post(lv, q, b.results[pod]);
           }
+          if constexpr (DIAG) {
+            // The FitError's diagnosis: pod q once more on each of my nodes, with phase 1's own evaluation.  Exact:
+            // the cores (and, for the generic path, the mirror columns) are what pod q's cycle saw -- pod q-1's
+            // assume was installed before the last barrier, by the thread that owns the node here too -- pod q
+            // assumes nothing, and its program is still in s_blob[q % 3].  No feasible node anywhere means every
+            // node was processed (a sampled pod's too), so the rows of all workgroups cover all N nodes.  The branch
+            // is workgroup-uniform; the waves meet through LDS adds and an arrival count (no barrier, no spin).
+            if (t < U) {
+              const bool fast = (d.flags & DF_FAST) != 0;
+              const PodFast pf = load_fast(base, d);
+              uint32_t mine = 0;
+              for (int kk = 0; kk < nk; ++kk) {
+                const int i = (k0 + kk) * U + t;
+                const bool valid = i < m.n;
+                uint32_t st = 0;
+                if (valid)
+                  st = fast ? eval_core_fast<NOM>(m, lds_core(s_core, kk, t), s_core.bwo[kk][t], pf, base, d, i).st
+                            : eval_node<false, NOM>(m, b, base, d, pod, i, true).st;
+                mine = diag_count(st, valid, mine);
+              }
+              diag_flush(mine, lv.diag + (size_t)pod * kDiagWords, s_dg, NW);
+            }
+          }
         } else if (wsl >= 0 && t == wsl % U) {  // chosen here, not assumed
           commit_result(m, b, base, d, rot_stats(pod, par), pod, F, win, s_best, nullptr, s_ipa);
           if constexpr (RING) ring_post(lv, q, b.results[pod]);
@@ -2982,10 +3076,12 @@ __device__ __forceinline__ void sched_loop_body(const MirrorView& m, const Batch
 // instances compiled without the overlay
 // SPLIT: the instance with NW more waves for phase 1's post evaluation (kSplitThreads threads)
 constexpr int kSplitThreads = 2 * (2 * 64) + 128;
-template <int NW, bool RING, int MS = kMaxSweep, bool NOM = false, bool SPLIT = false>
+// DIAG: the diagnosing instance (LoopView::diag set): the two split instances, and the unsplit ones built with the
+// overlay and every sweep round only
+template <int NW, bool RING, int MS = kMaxSweep, bool NOM = false, bool SPLIT = false, bool DIAG = false>
 __global__ __launch_bounds__(NW * 64 + 128 + (SPLIT ? NW * 64 : 0)) void k_sched_loop(MirrorView m, BatchView b, LoopView lv) {
   const LoopGroupArg& a = *(const LoopGroupArg*)__builtin_amdgcn_kernarg_segment_ptr();
-  sched_loop_body<NW, RING, MS, false, NOM, SPLIT>(a.m, a.b, a.lv, 0);
+  sched_loop_body<NW, RING, MS, false, NOM, SPLIT, DIAG>(a.m, a.b, a.lv, 0);
 }
 // In-process rank groups (localGroup: W contexts on one device): every rank's loop in ONE dispatch, block
 // r * G + w playing rank r's workgroup w with rank r's views.  Loops of separate dispatches on separate
@@ -5040,6 +5136,12 @@ hipError_t launch_nominated(const MirrorView& m, const BatchView& b, int pod, hi
   hipLaunchKernelGGL(k_nominated, dim3(1), dim3(64), 0, s, m, b, pod);
   return hipGetLastError();
 }
+hipError_t launch_diag_reduce(const MirrorView& m, const BatchView& b, int pod, int32_t* rows, hipStream_t s) {
+  const int nb = (m.n + kBlock - 1) / kBlock;
+  if (nb == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_diag_reduce, dim3(nb), dim3(kBlock), 0, s, m, b, pod, rows);
+  return hipGetLastError();
+}
 hipError_t launch_ob_store(const BatchView& b, int pod, hipStream_t s) {
   hipLaunchKernelGGL(k_ob_store, dim3(1), dim3(1024), 0, s, b, pod);
   return hipGetLastError();
@@ -5202,8 +5304,12 @@ hipError_t launch_max_reduce(unsigned long long* dst, const RankPtrs& src, int n
   return hipGetLastError();
 }
 // unit 128: 128-node workgroups (two evaluation waves, every role on a SIMD of its own); 256: four
+// (the diagnosing instances: defined last, so that they follow every other kernel in the code object)
+static hipError_t launch_sched_loop_diag(const MirrorView& m, const BatchView& b, const LoopView& lv, hipStream_t s,
+                                         hipEvent_t t0, hipEvent_t t1, int unit);
 hipError_t launch_sched_loop(const MirrorView& m, const BatchView& b, const LoopView& lv, hipStream_t s,
                              hipEvent_t t0, hipEvent_t t1, int unit) {
+  if (lv.diag != nullptr) return launch_sched_loop_diag(m, b, lv, s, t0, t1, unit);
   if (m.nom != nullptr) {  // a nominee table: the instances with the overlay (any number of sweep rounds)
     const dim3 grid(lv.nwg), blk(unit == 128 ? 2 * 64 + 128 : kLoopThreads);
     if (lv.ring) {
@@ -5316,15 +5422,19 @@ hipError_t loop_occupancy(int (&occ)[4]) {
   }
   // (k_sched_loop's instances with the nominee overlay use more registers, its split instances have six waves:
   // a grid must fit whichever is launched)
-  const K kn[4] = {{reinterpret_cast<const void*>(&k_sched_loop<2, false, kMaxSweep, true>), 2 * 64 + 128},
+  const K kn[8] = {{reinterpret_cast<const void*>(&k_sched_loop<2, false, kMaxSweep, true>), 2 * 64 + 128},
                    {reinterpret_cast<const void*>(&k_sched_loop<4, false, kMaxSweep, true>), kLoopThreads},
                    {reinterpret_cast<const void*>(&k_sched_loop<2, false, 1, false, true>), kSplitThreads},
-                   {reinterpret_cast<const void*>(&k_sched_loop<2, false, kMaxSweep, false, true>), kSplitThreads}};
-  for (int i = 0; i < 4; ++i) {
+                   {reinterpret_cast<const void*>(&k_sched_loop<2, false, kMaxSweep, false, true>), kSplitThreads},
+                   {reinterpret_cast<const void*>(&k_sched_loop<2, false, kMaxSweep, true, false, true>), 2 * 64 + 128},
+                   {reinterpret_cast<const void*>(&k_sched_loop<4, false, kMaxSweep, true, false, true>), kLoopThreads},
+                   {reinterpret_cast<const void*>(&k_sched_loop<2, false, 1, false, true, true>), kSplitThreads},
+                   {reinterpret_cast<const void*>(&k_sched_loop<2, false, kMaxSweep, false, true, true>), kSplitThreads}};
+  for (int i = 0; i < 8; ++i) {
     int o = 0;
     const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&o, kn[i].f, kn[i].threads, 0);
     if (e != hipSuccess) return e;
-    const int k = i < 2 ? i : 0;  // the split instances: 128-node units
+    const int k = i < 2 ? i : i == 5 ? 1 : 0;  // the split instances: 128-node units; [4..7] the diagnosing instances
     occ[k] = o < occ[k] ? o : occ[k];
   }
   return hipSuccess;
@@ -5357,19 +5467,37 @@ hipError_t warm_kernels() {
                       reinterpret_cast<const void*>(&k_agg_loop<false, false, false, 1>),
                       reinterpret_cast<const void*>(&k_gather_rows),        reinterpret_cast<const void*>(&k_gather_csr),
                       reinterpret_cast<const void*>(&k_ob_hint),            reinterpret_cast<const void*>(&k_ob_store),
-                      reinterpret_cast<const void*>(&k_nominated),
+                      reinterpret_cast<const void*>(&k_nominated),          reinterpret_cast<const void*>(&k_diag_reduce),
                       reinterpret_cast<const void*>(&k_sched_loop_group<2, 1>),
                       reinterpret_cast<const void*>(&k_sched_loop_group<2, kMaxSweep>),
                       reinterpret_cast<const void*>(&k_sched_loop_group<4, kMaxSweep>),
                       reinterpret_cast<const void*>(&k_agg_loop_group),
                       reinterpret_cast<const void*>(&k_put_group_arg<LoopGroupArg>),
                       reinterpret_cast<const void*>(&k_put_group_arg<AggGroupArg>),
-                      reinterpret_cast<const void*>(&k_ob_remap)};
+                      reinterpret_cast<const void*>(&k_ob_remap),
+                      reinterpret_cast<const void*>(&k_sched_loop<2, false, kMaxSweep, true, false, true>),
+                      reinterpret_cast<const void*>(&k_sched_loop<4, false, kMaxSweep, true, false, true>),
+                      reinterpret_cast<const void*>(&k_sched_loop<2, false, 1, false, true, true>),
+                      reinterpret_cast<const void*>(&k_sched_loop<2, false, kMaxSweep, false, true, true>)};
   for (const void* f : fs) {
     const hipError_t e = hipFuncGetAttributes(&a, f);
     if (e != hipSuccess) return e;
   }
   return hipSuccess;
+}
+// A diagnosed batch run (LoopView::diag; unsharded, never resident): k_sched_loop's diagnosing instances.
+static hipError_t launch_sched_loop_diag(const MirrorView& m, const BatchView& b, const LoopView& lv, hipStream_t s,
+                                         hipEvent_t t0, hipEvent_t t1, int unit) {
+  const dim3 grid(lv.nwg);
+  if (unit == 128 && lv.split_eval && lv.world == 1 && m.nom == nullptr) {  // the split instances, chosen as launch_sched_loop does
+    if (lv.nwg <= 64) hipExtLaunchKernelGGL((k_sched_loop<2, false, 1, false, true, true>), grid, dim3(kSplitThreads), 0, s, t0, t1, 0, m, b, lv);
+    else hipExtLaunchKernelGGL((k_sched_loop<2, false, kMaxSweep, false, true, true>), grid, dim3(kSplitThreads), 0, s, t0, t1, 0, m, b, lv);
+  } else if (unit == 128) {  // (the others: with the overlay, whether or not a nominee table is staged)
+    hipExtLaunchKernelGGL((k_sched_loop<2, false, kMaxSweep, true, false, true>), grid, dim3(2 * 64 + 128), 0, s, t0, t1, 0, m, b, lv);
+  } else {
+    hipExtLaunchKernelGGL((k_sched_loop<4, false, kMaxSweep, true, false, true>), grid, dim3(kLoopThreads), 0, s, t0, t1, 0, m, b, lv);
+  }
+  return hipGetLastError();
 }
 #ifdef KSG_DIAG
 hipError_t set_diag(unsigned long long* p) { return hipMemcpyToSymbol(HIP_SYMBOL(g_diag), &p, sizeof(p)); }

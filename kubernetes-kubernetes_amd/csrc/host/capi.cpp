@@ -257,8 +257,17 @@ int ksg_pod_release(ksg_ctx* ctx, int32_t handle) {
   return ctx->engine->queue.erase(handle) ? KSG_OK : KSG_ENOTFOUND;
 }
 
-int ksg_schedule_one(ksg_ctx* ctx, int32_t handle, uint32_t flags, ksg_result* result, ksg_eval_out* eval) {
-  if (!ctx || !result) return KSG_EINVAL;
+// a node-sharded context has no diagnosed cycles (the rows are reduced on one device's mirror)
+static int diag_refused(ksg_ctx* ctx) {
+  if (!ctx->engine->comm) return KSG_OK;
+  ctx->err = "ksg_schedule_one_diag / ksg_schedule_batch_diag on a node-sharded context";
+  return KSG_ENOTSUP;
+}
+
+// ksg_schedule_one (diag == NULL) / ksg_schedule_one_diag.  A diagnosed cycle takes the launch path: its status
+// words are stored and k_diag_reduce follows its k_select.
+static int schedule_one(ksg_ctx* ctx, int32_t handle, uint32_t flags, ksg_result* result, ksg_eval_out* eval,
+                        ksg_diagnosis* diag) {
   GUARD({
     auto it = ctx->engine->queue.find(handle);
     if (it == ctx->engine->queue.end()) return KSG_ENOTFOUND;
@@ -266,7 +275,7 @@ int ksg_schedule_one(ksg_ctx* ctx, int32_t handle, uint32_t flags, ksg_result* r
     // (a pod the nominator holds ends its nomination when it is assumed: the nominee table changes, which a
     // resident loop does not see -- it takes the launch path)
     const bool owner = ctx->engine->nom_evaluate() && ctx->engine->nom_owner(it->second);
-    if (!eval && (flags & KSG_FLAG_ASSUME) && !owner) {  // a resident loop (k_sched_loop / k_agg_loop), else the launch path
+    if (!eval && !diag && (flags & KSG_FLAG_ASSUME) && !owner) {  // a resident loop (k_sched_loop / k_agg_loop), else the launch path
       bool handled = false;
       const int rc = ctx->engine->schedule_resident(it->second, handle, result, &handled);
       if (handled) return with_err(ctx, rc);
@@ -274,12 +283,25 @@ int ksg_schedule_one(ksg_ctx* ctx, int32_t handle, uint32_t flags, ksg_result* r
     if (const int rs = quiesce(ctx)) return rs;
     std::vector<const PodSpec*> pods{&it->second};
     std::vector<int32_t> hs{handle};
-    return with_err(ctx, ctx->engine->run_batch_api(pods, hs, (flags & KSG_FLAG_ASSUME) != 0, result, eval));
+    return with_err(ctx, ctx->engine->run_batch_api(pods, hs, (flags & KSG_FLAG_ASSUME) != 0, result, eval, diag));
   })
 }
 
-int ksg_schedule_batch(ksg_ctx* ctx, const int32_t* handles, int32_t n, uint32_t flags, ksg_result* results) {
-  if (!ctx || n < 0 || (n && (!handles || !results))) return KSG_EINVAL;
+int ksg_schedule_one(ksg_ctx* ctx, int32_t handle, uint32_t flags, ksg_result* result, ksg_eval_out* eval) {
+  if (!ctx || !result) return KSG_EINVAL;
+  return schedule_one(ctx, handle, flags, result, eval, nullptr);
+}
+
+int ksg_schedule_one_diag(ksg_ctx* ctx, int32_t handle, uint32_t flags, ksg_result* result, ksg_eval_out* eval,
+                          ksg_diagnosis* diag) {
+  if (!ctx || !result || !diag) return KSG_EINVAL;
+  if (const int rd = diag_refused(ctx)) return rd;
+  return schedule_one(ctx, handle, flags, result, eval, diag);
+}
+
+// ksg_schedule_batch (diags == NULL) / ksg_schedule_batch_diag
+static int schedule_batch(ksg_ctx* ctx, const int32_t* handles, int32_t n, uint32_t flags, ksg_result* results,
+                          ksg_diagnosis* diags) {
   GUARD({
     if (const int rs = quiesce(ctx)) return rs;
     ctx->engine->api_t0_ = std::chrono::steady_clock::now();  // loopStamps: the handle lookups' share
@@ -302,7 +324,7 @@ int ksg_schedule_batch(ksg_ctx* ctx, const int32_t* handles, int32_t n, uint32_t
         if (i + 1 < n && !ctx->engine->nom_owner(*pods[(size_t)i])) continue;
         const std::vector<const PodSpec*> sub(pods.begin() + a, pods.begin() + i + 1);
         const std::vector<int32_t> sh(hs.begin() + a, hs.begin() + i + 1);
-        const int rc = ctx->engine->run_batch_api(sub, sh, assume, results + a, nullptr);
+        const int rc = ctx->engine->run_batch_api(sub, sh, assume, results + a, nullptr, diags ? diags + a : nullptr);
         if (rc != KSG_OK) {  // as a loop give-up leaves a batch: the pods after the failed run are not scheduled
           for (int32_t j = i + 1; j < n; ++j) results[j] = not_scheduled();
           return with_err(ctx, rc);
@@ -311,8 +333,20 @@ int ksg_schedule_batch(ksg_ctx* ctx, const int32_t* handles, int32_t n, uint32_t
       }
       return with_err(ctx, KSG_OK);
     }
-    return with_err(ctx, ctx->engine->run_batch_api(pods, hs, assume, results, nullptr));
+    return with_err(ctx, ctx->engine->run_batch_api(pods, hs, assume, results, nullptr, diags));
   })
+}
+
+int ksg_schedule_batch(ksg_ctx* ctx, const int32_t* handles, int32_t n, uint32_t flags, ksg_result* results) {
+  if (!ctx || n < 0 || (n && (!handles || !results))) return KSG_EINVAL;
+  return schedule_batch(ctx, handles, n, flags, results, nullptr);
+}
+
+int ksg_schedule_batch_diag(ksg_ctx* ctx, const int32_t* handles, int32_t n, uint32_t flags, ksg_result* results,
+                            ksg_diagnosis* diags) {
+  if (!ctx || n < 0 || (n && (!handles || !results || !diags))) return KSG_EINVAL;
+  if (const int rd = diag_refused(ctx)) return rd;
+  return schedule_batch(ctx, handles, n, flags, results, diags);
 }
 
 int ksg_forget(ksg_ctx* ctx, int32_t handle) {  // Cache.ForgetPod (backend/cache/cache.go:412-434)

@@ -79,6 +79,7 @@ hipError_t warm_aggregate();
 hipError_t launch_ob_hint(const MirrorView& m, const BatchView& b, int pod, hipStream_t s);
 hipError_t launch_nominated(const MirrorView& m, const BatchView& b, int pod, hipStream_t s);
 hipError_t launch_ob_store(const BatchView& b, int pod, hipStream_t s);
+hipError_t launch_diag_reduce(const MirrorView& m, const BatchView& b, int pod, int32_t* rows, hipStream_t s);
 hipError_t launch_ob_remap(ObState* st, ObEnt* h, const int32_t* map, int nold, int maxlen, hipStream_t s);
 hipError_t loop_occupancy(int (&occ)[4]);
 
@@ -1258,10 +1259,11 @@ Engine::~Engine() {
   for (DevBuf* b : {&d_descs, &d_meta, &d_status, &d_fmask, &d_blk, &d_fixed, &d_raw, &d_out,
                     &d_total, &d_arena, &d_xa, &d_xp, &d_xb, &d_xs, &d_gran, &d_fail, &d_grp, &d_agran, &d_region, &d_astamps, &d_aspill, &d_relay,
                     &d_evg, &d_aggpeers, &d_pre, &d_seg, &d_segcnt, &d_psout, &d_pdb, &d_pick, &d_contrib_buf, &d_wide, &d_vsc,
-                    &d_ob, &d_ob_heap, &d_ob_map, &d_tcache, &d_tcw, &d_nom})
+                    &d_ob, &d_ob_heap, &d_ob_map, &d_tcache, &d_tcw, &d_nom, &d_diag})
     if (b->p) (void)hipFree(b->p);
   if (h_pinned) (void)hipHostFree(h_pinned);
   if (h_tcw) (void)hipHostFree(h_tcw);
+  if (h_diag) (void)hipHostFree(h_diag);
   if (ev0) (void)hipEventDestroy(ev0);
   if (ev1) (void)hipEventDestroy(ev1);
 }
@@ -1812,10 +1814,10 @@ int Engine::nom_sync() {
 void Engine::nom_off() { c->view.nom = nullptr; }
 
 int Engine::run_batch_api(const std::vector<const PodSpec*>& pods, const std::vector<int32_t>& handles, bool assume,
-                          ksg_result* results, ksg_eval_out* eval) {
+                          ksg_result* results, ksg_eval_out* eval, ksg_diagnosis* diag) {
   fault_first_ = -1;
   htrace("batch", (long)pods.size());
-  const int rc = run_batch(pods, handles, assume, results, eval);
+  const int rc = run_batch(pods, handles, assume, results, eval, diag);
   htrace("ret", rc < 0 ? -rc : rc);
   htrace_flush(comm ? c->cfg.rank : 0);
   if (fault_first_ >= 0) ++loop_give_ups_;
@@ -1859,10 +1861,15 @@ int Engine::run_batch_api(const std::vector<const PodSpec*>& pods, const std::ve
 }
 
 int Engine::run_batch(const std::vector<const PodSpec*>& pods, const std::vector<int32_t>& handles, bool assume,
-                      ksg_result* results, ksg_eval_out* eval) {
+                      ksg_result* results, ksg_eval_out* eval, ksg_diagnosis* diag) {
   const int n = (int)pods.size();
   if (n == 0) return KSG_OK;
   if (eval && n != 1) return KSG_EINVAL;
+  if (diag && comm) {
+    c->err = "FitError diagnosis on a node-sharded context";
+    return KSG_ENOTSUP;
+  }
+  if (diag) std::memset(diag, 0, (size_t)n * sizeof(ksg_diagnosis));
   struct NomReset {
     bool* f;
     ~NomReset() { *f = false; }
@@ -1872,6 +1879,7 @@ int Engine::run_batch(const std::vector<const PodSpec*>& pods, const std::vector
   nom_prepare();
   if (c->order().empty()) {  // ErrNoNodesAvailable (schedule_one.go:569-571)
     for (int i = 0; i < n; ++i) results[i] = ksg_result{KSG_CODE_ERROR, -1, 0, 0, 0};
+    for (int i = 0; i < n && diag; ++i) diag[i].prefilter_plugin = KSG_PLUGIN_NONE;
     return KSG_OK;
   }
   using clk = std::chrono::steady_clock;
@@ -1955,6 +1963,7 @@ int Engine::run_batch(const std::vector<const PodSpec*>& pods, const std::vector
       const int rc = compile(*pods[i], CYCLE, -1, assume, eval != nullptr, &cp[i]);
       next_slot_ = -1;
       if (rc) return rc;
+      if (diag) reinterpret_cast<PodDesc*>(cp[i].blob.data())->flags |= DF_DIAG;
       if (cp[i].prefilter_error) cp[i].error = true;  // PreFilter Error: status Error, no launch
       if (ob_on) ob_sequence(cp[i], *pods[i], ob_now());
       if (!cp[i].prefilter_reject && !cp[i].prefilter_error && !rotdev()) {
@@ -2171,6 +2180,8 @@ int Engine::run_batch(const std::vector<const PodSpec*>& pods, const std::vector
   // grid, as those share this device -- must fit in what the CUs hold at once (loop_occ); a grid that
   // does not is never launched, instead of spinning until the give-up
   const int64_t dev_ranks = comm && !rccl ? W : 1;
+  // (a diagnosed call: k_sched_loop's diagnosing instances; k_agg_loop's class runs on the per-pod launches,
+  // k_diag_reduce behind each pod's k_select)
   const bool use_loop = loop_worth && (!comm || dx) && !eval && c->cfg.persistent_loop && NB > 0 && GS >= 1 &&
                         (int64_t)GS * kLoopMaxBlk * unit >= (int64_t)NBs * kBlock &&
                         (int64_t)GS * dev_ranks <= (int64_t)cus * loop_occ[unit == 128 ? 0 : 1] &&
@@ -2179,7 +2190,7 @@ int Engine::run_batch(const std::vector<const PodSpec*>& pods, const std::vector
   // every workgroup's LDS lists must hold its nodes' pods and terms plus everything this batch can add
   // (each pod, and its own terms, at most once).  Every rank decides alike: the check covers every
   // rank's workgroups (each rank holds the whole cluster).
-  bool use_agg = loop_worth && (!comm || dx) && !eval && c->cfg.persistent_loop && c->cfg.agg_loop && NB > 0 && G >= 1 &&
+  bool use_agg = loop_worth && !diag && (!comm || dx) && !eval && c->cfg.persistent_loop && c->cfg.agg_loop && NB > 0 && G >= 1 &&
                  G * W <= std::min(cus, 256) && (int64_t)G * kLoopMaxBlk >= NBs &&
                  (int64_t)G * dev_ranks <= (int64_t)cus * loop_occ[W > 1 ? 3 : 2] &&
                  (int64_t)c->taint_max_per_node < ((int64_t)1 << 24) - 1;
@@ -2242,6 +2253,17 @@ int Engine::run_batch(const std::vector<const PodSpec*>& pods, const std::vector
 #endif
     }
   }
+  if (diag) {  // the rows: zeroed per call, only ever added to by the kernels
+    if ((rc = ensure(d_diag, (size_t)n * kDiagWords * 4))) return rc;
+    HIPCHK(hipMemsetAsync(d_diag.p, 0, (size_t)n * kDiagWords * 4, s));
+    if (h_diag_rows < (size_t)n) {
+      if (h_diag) (void)hipHostFree(h_diag);
+      h_diag = nullptr;
+      h_diag_rows = 0;
+      HIPCHK(hipHostMalloc((void**)&h_diag, (size_t)n * 2 * kDiagWords * 4, hipHostMallocDefault));
+      h_diag_rows = (size_t)n * 2;
+    }
+  }
   struct Chunk { int a, b; };
   std::vector<Chunk> chunks;
   while (cev.size() < bnd.size()) {
@@ -2261,6 +2283,9 @@ int Engine::run_batch(const std::vector<const PodSpec*>& pods, const std::vector
     HIPCHK(hipMemcpyAsync(hr + a, (DevResult*)d_results.p + a, (size_t)(upto - a) * sizeof(DevResult),
                           hipMemcpyDeviceToHost, ds));
     if (use_loop || use_agg) HIPCHK(hipMemcpyAsync(hfail + chunks.size(), d_fail.p, 4, hipMemcpyDeviceToHost, ds));
+    if (diag)  // the chunk's rows, in the same step as its results
+      HIPCHK(hipMemcpyAsync(h_diag + (size_t)a * kDiagWords, (int32_t*)d_diag.p + (size_t)a * kDiagWords,
+                            (size_t)(upto - a) * kDiagWords * 4, hipMemcpyDeviceToHost, ds));
     HIPCHK(hipEventRecord(cev[chunks.size()], ds));
     chunks.push_back({a, upto});
     return KSG_OK;
@@ -2273,6 +2298,23 @@ int Engine::run_batch(const std::vector<const PodSpec*>& pods, const std::vector
       double* t; clk::time_point s;
       ~Acc() { *t += std::chrono::duration<double, std::micro>(clk::now() - s).count(); }
     } acc_{&settle_us, Ts};
+    // the diagnosis of pod i from its row, once its result is final (every counter 0 unless a FitError)
+    auto diagnose = [&](int i) {
+      ksg_diagnosis& g = diag[i];
+      g.num_nodes = m.n;
+      g.prefilter_code = cp[i].prefilter_reject ? cp[i].prefilter_code : 0;
+      g.prefilter_plugin = cp[i].prefilter_reject ? cp[i].prefilter_plugin : KSG_PLUGIN_NONE;
+      const int32_t st = results[i].status;
+      if (cp[i].error || (st != KSG_CODE_UNSCHEDULABLE && st != KSG_CODE_UNSCHEDULABLE_AND_UNRESOLVABLE)) return;
+      const int32_t* row = h_diag + (size_t)i * kDiagWords;
+      g.failed_nodes = row[DG_FAILED];
+      g.unresolvable_nodes = row[DG_UNRES];
+      for (int q = 0; q < kNumPlugins; ++q) {
+        g.plugin_nodes[q] = row[DG_PLUGIN + q];
+        if (row[DG_PLUGIN + q] > 0) g.unschedulable_plugins |= 1u << q;
+      }
+      for (int q = 0; q < kNumReasons; ++q) g.reason_nodes[q] = row[DG_REASON + q];
+    };
     for (int i = a; i < b; ++i) {
       ksg_result& r = results[i];
       if (cp[i].error) {
@@ -2312,6 +2354,7 @@ int Engine::run_batch(const std::vector<const PodSpec*>& pods, const std::vector
         c->pod_table_drop(cp[i].slot);  // not placed: the reserved pod-table slot never went live
       }
     }
+    for (int i = a; i < b && diag; ++i) diagnose(i);
     return KSG_OK;
   };
   // A persistent loop gave up (a workgroup never reached an exchange): pods [first, n) are not
@@ -2459,6 +2502,7 @@ int Engine::run_batch(const std::vector<const PodSpec*>& pods, const std::vector
       lv.wave_map = c->cfg.loop_wave_map;
       // the split instance: unsharded 128-node-unit runs without a nominee table (launch_sched_loop)
       lv.split_eval = c->cfg.loop_split_eval && unit == 128 && W == 1 && !comm && m.nom == nullptr ? 1 : 0;
+      lv.diag = diag ? (int32_t*)d_diag.p : nullptr;  // the diagnosing instance (launch_sched_loop)
       lv.wstamps = c->cfg.loop_stamps ? (unsigned long long*)d_stamps.p + (size_t)n * 8 + 64 + (size_t)i * GS * 8 : nullptr;
       // in-process ranks: every rank is past its allocations before any rank's first loop starts
       if ((runs.empty() || regate) && comm) htrace("gate", i);
@@ -2597,6 +2641,7 @@ int Engine::run_batch(const std::vector<const PodSpec*>& pods, const std::vector
     if (hd.score_mask & (1u << P_PTS)) HIPCHK(launch_pts_score(m, bv, i, s));
     HIPCHK(launch_select(m, bv, i, s, lds));
     if (hd.flags & DF_OB) HIPCHK(launch_ob_store(bv, i, s));  // StoreScheduleResults
+    if (diag) HIPCHK(launch_diag_reduce(m, bv, i, (int32_t*)d_diag.p, s));  // reads the pod's outcome on the device
     bytes += algo_bytes(hd);
     launches++;
     ++i;

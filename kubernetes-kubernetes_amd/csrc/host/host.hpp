@@ -584,13 +584,15 @@ class Engine {
   int compile_topology(const PodSpec& p, Mode mode, int plugin, int32_t N, Blob* B, PodDesc* D, uint32_t* fmask,
                        uint32_t* smask, CompiledPod* out);
   // run a batch of cycles (device-resident, sequential semantics)
+  // diag (ksg_schedule_*_diag, [pods]): every pod's FitError diagnosis as of its own cycle, reduced on the device
+  // (DESIGN.md §4.11); unsharded contexts only
   int run_batch(const std::vector<const PodSpec*>& pods, const std::vector<int32_t>& handles, bool assume,
-                ksg_result* results, ksg_eval_out* eval);
+                ksg_result* results, ksg_eval_out* eval, ksg_diagnosis* diag = nullptr);
   // run_batch, and for an in-process rank group whose persistent loop gave up (its ranks' loops could not all
   // be resident at once: HIP gives no control over which hardware queue a stream lands on), the pods from the
   // failed chunk on once more over the all-reduce path
   int run_batch_api(const std::vector<const PodSpec*>& pods, const std::vector<int32_t>& handles, bool assume,
-                    ksg_result* results, ksg_eval_out* eval);
+                    ksg_result* results, ksg_eval_out* eval, ksg_diagnosis* diag = nullptr);
   int fault_first_ = -1;        // the first pod loop_fault left unscheduled (-1: none), for run_batch_api
   bool force_allreduce_ = false;  // run_batch_api's retry: no device exchange
   uint64_t loop_retries_ = 0;   // batches run_batch_api re-ran over the all-reduce path
@@ -654,6 +656,9 @@ class Engine {
   DevBuf d_ob, d_ob_heap, d_ob_map;      // OpportunisticBatching: ObState, ObEnt[cap], the remap
   DevBuf d_meta;                         // owns the three views below (ensure_scratch)
   DevBuf d_off, d_stats, d_results;      // views: program offsets + sizes, PodStats, DevResult
+  DevBuf d_diag;                         // diagnosed calls: one kDiagWords row per pod (k_diag_reduce)
+  int32_t* h_diag = nullptr;             // their pinned landing area
+  size_t h_diag_rows = 0;
   DevBuf d_arena;  // PTS/IPA histograms; kept all-zero between pods (k_select re-zeroes what it used)
   DevBuf d_xa, d_xp, d_xb, d_xs;  // node-sharded exchange vectors, one set per pod of the batch
   DevBuf d_evg;             // node-sharded evaluation output, gathered over the ranks

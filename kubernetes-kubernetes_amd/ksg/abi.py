@@ -43,6 +43,8 @@ REASONS = [
     "PreFilter",
 ]
 
+NUM_REASONS = len(REASONS)
+
 FLAG_ASSUME = 1
 
 
@@ -90,6 +92,36 @@ class EvalOut(C.Structure):
         ("total_scores", C.POINTER(C.c_int64)),
         ("normalized_scores", C.POINTER(C.c_int64)),
     ]
+
+
+class Diagnosis(C.Structure):
+    """ksg_diagnosis: one cycle's FitError, reduced on the device (ksg.h)."""
+    _fields_ = [
+        ("num_nodes", C.c_int32),
+        ("failed_nodes", C.c_int32),
+        ("unresolvable_nodes", C.c_int32),
+        ("unschedulable_plugins", C.c_uint32),
+        ("prefilter_code", C.c_int32),
+        ("prefilter_plugin", C.c_int32),
+        ("plugin_nodes", C.c_int32 * NUM_PLUGINS),
+        ("reason_nodes", C.c_int32 * NUM_REASONS),
+    ]
+
+    def as_dict(self):
+        return {
+            "num_nodes": self.num_nodes,
+            "failed_nodes": self.failed_nodes,
+            "unresolvable_nodes": self.unresolvable_nodes,
+            "unschedulable_plugins": self.unschedulable_plugins,
+            "prefilter_code": self.prefilter_code,
+            "prefilter_plugin": self.prefilter_plugin,
+            "plugin_nodes": list(self.plugin_nodes),
+            "reason_nodes": list(self.reason_nodes),
+        }
+
+    def plugins(self):
+        """Diagnosis.UnschedulablePlugins as plugin names."""
+        return [PLUGINS[p] for p in range(NUM_PLUGINS) if (self.unschedulable_plugins >> p) & 1]
 
 
 def _sig(lib, prefix):
@@ -238,21 +270,23 @@ class Backend:
     def schedule_one(self, handle, assume=True, evaluate=False):
         """Returns (Result, eval dict or None)."""
         r = Result()
-        ev = None
-        evp = None
-        if evaluate:
-            n = self.num_nodes()
-            code = (C.c_uint8 * n)()
-            plug = (C.c_uint8 * n)()
-            reas = (C.c_uint32 * n)()
-            ps = (C.c_int64 * (n * NUM_PLUGINS))()
-            tot = (C.c_int64 * n)()
-            nrm = (C.c_int64 * (n * NUM_PLUGINS))()
-            ev = EvalOut(0, 0, code, plug, reas, 0, ps, tot, nrm)
-            evp = C.byref(ev)
+        ev = self._eval_alloc() if evaluate else None
+        evp = C.byref(ev) if evaluate else None
         self._chk(self.f["schedule_one"](self.ctx, handle, FLAG_ASSUME if assume else 0, C.byref(r), evp), "schedule_one")
-        if not evaluate:
-            return r, None
+        return r, (self._eval_dict(ev) if evaluate else None)
+
+    def _eval_alloc(self):
+        """A ksg_eval_out with every array allocated for the current snapshot."""
+        n = self.num_nodes()
+        code = (C.c_uint8 * n)()
+        plug = (C.c_uint8 * n)()
+        reas = (C.c_uint32 * n)()
+        ps = (C.c_int64 * (n * NUM_PLUGINS))()
+        tot = (C.c_int64 * n)()
+        nrm = (C.c_int64 * (n * NUM_PLUGINS))()
+        return EvalOut(0, 0, code, plug, reas, 0, ps, tot, nrm)
+
+    def _eval_dict(self, ev):
         n = self.num_nodes()
         out = {
             "prefilter_code": ev.prefilter_code,
@@ -265,7 +299,7 @@ class Backend:
             "total_scores": [ev.total_scores[i] for i in range(n)],
             "normalized_scores": [[ev.normalized_scores[p * n + i] for i in range(n)] for p in range(NUM_PLUGINS)],
         }
-        return r, out
+        return out
 
     def schedule_batch(self, handles, assume=True):
         n = len(handles)

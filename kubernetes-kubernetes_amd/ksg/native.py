@@ -49,11 +49,49 @@ def load():
     return _lib
 
 
+def _diag_calls():
+    """ksg_schedule_one_diag / ksg_schedule_batch_diag (ABI 3), bound on first use: not in abi._sig, which the
+    oracle's library shares, and not in load(), so that KSG_LIB may still name a library built before them."""
+    lib = load()
+    if not getattr(lib, "_ksg_diag_bound", False):
+        from .abi import Diagnosis, EvalOut, Result
+        lib.ksg_schedule_one_diag.restype = C.c_int
+        lib.ksg_schedule_one_diag.argtypes = [C.c_void_p, C.c_int32, C.c_uint32, C.POINTER(Result), C.POINTER(EvalOut),
+                                              C.POINTER(Diagnosis)]
+        lib.ksg_schedule_batch_diag.restype = C.c_int
+        lib.ksg_schedule_batch_diag.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.c_int32, C.c_uint32,
+                                                C.POINTER(Result), C.POINTER(Diagnosis)]
+        lib._ksg_diag_bound = True
+    return lib.ksg_schedule_one_diag, lib.ksg_schedule_batch_diag
+
+
 class Scheduler(Backend):
     """One kube-scheduler profile + cache mirror resident in HBM (ksg_create)."""
 
     def __init__(self, config=None):
         super().__init__(load(), "ksg_", config)
+
+    def schedule_one_diag(self, handle, assume=True, evaluate=False):
+        """ksg_schedule_one_diag -> (Result, eval dict or None, Diagnosis): the cycle with its FitError reduced on
+        the device (every counter 0 unless the cycle ended unschedulable)."""
+        from .abi import FLAG_ASSUME, Diagnosis, Result
+        r, dg = Result(), Diagnosis()
+        ev = self._eval_alloc() if evaluate else None
+        self._chk(_diag_calls()[0](self.ctx, handle, FLAG_ASSUME if assume else 0, C.byref(r),
+                                                 C.byref(ev) if evaluate else None, C.byref(dg)), "schedule_one_diag")
+        return r, (self._eval_dict(ev) if evaluate else None), dg
+
+    def schedule_batch_diag(self, handles, assume=True):
+        """ksg_schedule_batch_diag -> ([Result], [Diagnosis]): pod i's diagnosis is as of its own cycle (the
+        assumes of pods 0..i-1 applied, none later)."""
+        from .abi import FLAG_ASSUME, Diagnosis, Result
+        n = len(handles)
+        hs = (C.c_int32 * n)(*handles)
+        rs = (Result * n)()
+        ds = (Diagnosis * n)()
+        self._chk(_diag_calls()[1](self.ctx, hs, n, FLAG_ASSUME if assume else 0, rs, ds),
+                  "schedule_batch_diag")
+        return [rs[i] for i in range(n)], [ds[i] for i in range(n)]
 
     def kernel_stats(self):
         """(avg ms, algorithmic bytes, launches, kernel name) of the last batch: per k_filter_score
