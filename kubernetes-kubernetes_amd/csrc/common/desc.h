@@ -766,6 +766,9 @@ struct AggView {
   // template's counts as this workgroup holds them; tcw[batch pod] the host's plan (TcWord; nullptr: off)
   unsigned long long* tcache;
   const uint32_t* tcw;
+  // a diagnosed batch run (ksg_schedule_batch_diag): the batch's diagnosis rows, [batch pods][kDiagWords] -- the
+  // DIAG instances add the statuses phase 1 computed to the pod's row where its cycle ends without a feasible node
+  int32_t* diag;
 };
 // In-process rank groups (localGroup, one device) run every rank's persistent loop in one dispatch
 // (k_sched_loop_group / k_agg_loop_group): rank r's launch arguments, [world] of them in device

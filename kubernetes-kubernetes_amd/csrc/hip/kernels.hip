@@ -3298,9 +3298,12 @@ __device__ __forceinline__ void apply_entry(const MirrorView& m, const uint8_t* 
 // end of the pod before it), no staging ahead.
 // MS: sweep rounds of 64 participants (kMaxSweep = 4: up to 256; the 1-round instance for grids of at most 64
 // workgroups holds a quarter of the exchange registers, which pays for the PodTopologySpread PX skip, as in RING)
+// DIAG: a diagnosed batch run (AggView::diag): phase 1's packed Filter statuses are held in LDS, and where a pod's
+// cycle ends without a feasible node wave 0 of every workgroup adds its nodes' statuses to the pod's row.
 // (the body of k_agg_loop and k_agg_loop_group: w = the workgroup this block plays in its rank)
-template <bool SHARD, bool PTSS, bool RING, int MS, bool GRP>
+template <bool SHARD, bool PTSS, bool RING, int MS, bool GRP, bool DIAG = false>
 __device__ __forceinline__ void agg_loop_body(const MirrorView& m, const BatchView& b, const AggView& av, const int w_grp) {
+  static_assert(!DIAG || (!RING && !SHARD && !GRP), "the diagnosing instances: unsharded batch runs");
   constexpr bool kPxa = RING || MS < kMaxSweep;  // phase 1 guesses the PTS raw scores (AG_PXA)
   constexpr int kBlob = RING ? kBlobLds : kAggBlobLds;       // program slot bytes (desc.h)
   constexpr uint32_t kLp = RING ? kAggRingPods : kAggPods;     // LDS list entries (the rest spill to HBM)
@@ -3313,6 +3316,8 @@ __device__ __forceinline__ void agg_loop_body(const MirrorView& m, const BatchVi
   __shared__ __align__(16) SlotVal s_sv[kAggSlots];
   __shared__ int64_t s_ri[kAggSlots];
   __shared__ unsigned long long s_ball[kAggThreads / 64];  // [wave] feasibility ballots
+  __shared__ uint32_t s_st[DIAG ? kAggThreads : 1];        // DIAG: [slot] phase 1's packed Filter status (0: feasible,
+                                                           // or no node in the slot)
   __shared__ int32_t s_lh[kAggLocal * kAggSlots];          // node-local histograms
   __shared__ unsigned long long s_gh[kAggGWords];          // shared-region partials, then totals
   __shared__ __align__(16) uint16_t s_elig[kAggSlots];     // eligibility per node: DoNotSchedule c (bit c),
@@ -4342,6 +4347,7 @@ __device__ __forceinline__ void agg_loop_body(const MirrorView& m, const BatchVi
         const unsigned long long bm = lim <= 0 ? 0ull : lim >= 64 ? ~0ull : ((1ull << lim) - 1ull);
         s_sv[t] = SlotVal{ne.fixed, (uint32_t)ne.rt, (uint32_t)ne.rna};
         s_ri[t] = ne.ripa;
+        if constexpr (DIAG) s_st[t] = my_node ? ne.st : 0u;
         unsigned long long et = 0, en = 0, ei = 0, ni = ~0ull;
         if (feas) {
           et = enc_i64(ne.rt);
@@ -4811,6 +4817,25 @@ __device__ __forceinline__ void agg_loop_body(const MirrorView& m, const BatchVi
             __hip_atomic_store(&s_bn_q, q, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
           }
         }
+        if constexpr (DIAG) {
+          // The FitError's diagnosis: the statuses phase 1 of pod q stored, one per slot of this workgroup (s_st).
+          // They are pod q's: phase 1 ran against the state pod q's cycle sees (pod q-1 folded, no evaluation ahead of
+          // a placement in this loop), and the next store to s_st is phase 1 of pod q+1, behind this iteration's
+          // closing barrier, which this wave has not reached yet.  F is exchange A's global count, the same in every
+          // workgroup, so all of them take the branch and their rows cover all the nodes; one wave does a workgroup's
+          // share, so no meeting point is needed.  Wave-uniform (okb, F): every lane takes part in the ballots.
+          if (okb && F == 0) {
+            uint32_t mine = 0;
+#pragma unroll 1
+            for (int v = 0; v < kAggThreads / 64; ++v) {
+              const uint32_t st = s_st[v * 64 + lane];
+              mine = diag_count(st, st != 0u, mine);
+            }
+            if (lane < DG_BINS && mine)
+              (void)__hip_atomic_fetch_add(av.diag + (size_t)pod * kDiagWords + lane, (int32_t)mine, __ATOMIC_RELAXED,
+                                           __HIP_MEMORY_SCOPE_AGENT);
+          }
+        }
         stamp(q, 4);
         if (lane == 0) wstamp(q, 3);
       }
@@ -5084,10 +5109,11 @@ __device__ __forceinline__ void agg_loop_body(const MirrorView& m, const BatchVi
     stamp(q, 8);
   }
 }
-template <bool SHARD, bool PTSS, bool RING = false, int MS = kMaxSweep>
+// DIAG: the diagnosing instance (AggView::diag set): the twins of the four unsharded batch instances
+template <bool SHARD, bool PTSS, bool RING = false, int MS = kMaxSweep, bool DIAG = false>
 __global__ __launch_bounds__(kAggThreads) void k_agg_loop(MirrorView m, BatchView b, AggView av) {
   const AggGroupArg& a = *(const AggGroupArg*)__builtin_amdgcn_kernarg_segment_ptr();  // (k_sched_loop)
-  agg_loop_body<SHARD, PTSS, RING, MS, false>(a.m, a.b, a.av, 0);
+  agg_loop_body<SHARD, PTSS, RING, MS, false, DIAG>(a.m, a.b, a.av, 0);
 }
 // In-process rank groups: every rank's node-sharded k_agg_loop in one dispatch (k_sched_loop_group)
 __global__ __launch_bounds__(kAggThreads) void k_agg_loop_group(const AggGroupArg* __restrict__ ga, int G) {
@@ -5356,8 +5382,12 @@ hipError_t launch_sched_loop(const MirrorView& m, const BatchView& b, const Loop
   }
   return hipGetLastError();
 }
+// (the diagnosing instances: defined last, as launch_sched_loop_diag)
+static hipError_t launch_agg_loop_diag(const MirrorView& m, const BatchView& b, const AggView& av, hipStream_t s,
+                                       hipEvent_t t0, hipEvent_t t1);
 hipError_t launch_agg_loop(const MirrorView& m, const BatchView& b, const AggView& av, hipStream_t s, hipEvent_t t0,
                            hipEvent_t t1) {
+  if (av.diag != nullptr) return launch_agg_loop_diag(m, b, av, s, t0, t1);
   auto go = [&](auto kern) {
     if (t0)
       hipExtLaunchKernelGGL(kern, dim3(av.nwg), dim3(kAggThreads), 0, s, t0, t1, 0, m, b, av);
@@ -5437,6 +5467,17 @@ hipError_t loop_occupancy(int (&occ)[4]) {
     const int k = i < 2 ? i : i == 5 ? 1 : 0;  // the split instances: 128-node units; [4..7] the diagnosing instances
     occ[k] = o < occ[k] ? o : occ[k];
   }
+  // (k_agg_loop's diagnosing instances hold 2 KB more LDS)
+  const void* ka[4] = {reinterpret_cast<const void*>(&k_agg_loop<false, true, false, 1, true>),
+                       reinterpret_cast<const void*>(&k_agg_loop<false, true, false, kMaxSweep, true>),
+                       reinterpret_cast<const void*>(&k_agg_loop<false, false, false, 1, true>),
+                       reinterpret_cast<const void*>(&k_agg_loop<false, false, false, kMaxSweep, true>)};
+  for (int i = 0; i < 4; ++i) {
+    int o = 0;
+    const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&o, ka[i], kAggThreads, 0);
+    if (e != hipSuccess) return e;
+    occ[2] = o < occ[2] ? o : occ[2];
+  }
   return hipSuccess;
 }
 // Loads the module's code object onto the current device now (hipFuncGetAttributes), so that no
@@ -5478,7 +5519,11 @@ hipError_t warm_kernels() {
                       reinterpret_cast<const void*>(&k_sched_loop<2, false, kMaxSweep, true, false, true>),
                       reinterpret_cast<const void*>(&k_sched_loop<4, false, kMaxSweep, true, false, true>),
                       reinterpret_cast<const void*>(&k_sched_loop<2, false, 1, false, true, true>),
-                      reinterpret_cast<const void*>(&k_sched_loop<2, false, kMaxSweep, false, true, true>)};
+                      reinterpret_cast<const void*>(&k_sched_loop<2, false, kMaxSweep, false, true, true>),
+                      reinterpret_cast<const void*>(&k_agg_loop<false, true, false, 1, true>),
+                      reinterpret_cast<const void*>(&k_agg_loop<false, true, false, kMaxSweep, true>),
+                      reinterpret_cast<const void*>(&k_agg_loop<false, false, false, 1, true>),
+                      reinterpret_cast<const void*>(&k_agg_loop<false, false, false, kMaxSweep, true>)};
   for (const void* f : fs) {
     const hipError_t e = hipFuncGetAttributes(&a, f);
     if (e != hipSuccess) return e;
@@ -5497,6 +5542,23 @@ static hipError_t launch_sched_loop_diag(const MirrorView& m, const BatchView& b
   } else {
     hipExtLaunchKernelGGL((k_sched_loop<4, false, kMaxSweep, true, false, true>), grid, dim3(kLoopThreads), 0, s, t0, t1, 0, m, b, lv);
   }
+  return hipGetLastError();
+}
+// A diagnosed batch run (AggView::diag; unsharded, never resident): k_agg_loop's diagnosing instances, chosen as
+// launch_agg_loop chooses among the unsharded batch instances.
+static hipError_t launch_agg_loop_diag(const MirrorView& m, const BatchView& b, const AggView& av, hipStream_t s,
+                                       hipEvent_t t0, hipEvent_t t1) {
+  if (av.ring != nullptr || av.world > 1) return hipErrorInvalidValue;
+  auto go = [&](auto kern) {
+    if (t0)
+      hipExtLaunchKernelGGL(kern, dim3(av.nwg), dim3(kAggThreads), 0, s, t0, t1, 0, m, b, av);
+    else
+      hipLaunchKernelGGL(kern, dim3(av.nwg), dim3(kAggThreads), 0, s, m, b, av);
+  };
+  if (av.ptss && av.nwg <= 64) go(k_agg_loop<false, true, false, 1, true>);
+  else if (av.ptss) go(k_agg_loop<false, true, false, kMaxSweep, true>);
+  else if (av.nwg <= 64) go(k_agg_loop<false, false, false, 1, true>);
+  else go(k_agg_loop<false, false, false, kMaxSweep, true>);
   return hipGetLastError();
 }
 #ifdef KSG_DIAG

@@ -2180,8 +2180,8 @@ int Engine::run_batch(const std::vector<const PodSpec*>& pods, const std::vector
   // grid, as those share this device -- must fit in what the CUs hold at once (loop_occ); a grid that
   // does not is never launched, instead of spinning until the give-up
   const int64_t dev_ranks = comm && !rccl ? W : 1;
-  // (a diagnosed call: k_sched_loop's diagnosing instances; k_agg_loop's class runs on the per-pod launches,
-  // k_diag_reduce behind each pod's k_select)
+  // (a diagnosed call: the loops' diagnosing instances reduce inside the loop; only the pods neither loop takes run
+  // on the per-pod launches, k_diag_reduce behind each pod's k_select)
   const bool use_loop = loop_worth && (!comm || dx) && !eval && c->cfg.persistent_loop && NB > 0 && GS >= 1 &&
                         (int64_t)GS * kLoopMaxBlk * unit >= (int64_t)NBs * kBlock &&
                         (int64_t)GS * dev_ranks <= (int64_t)cus * loop_occ[unit == 128 ? 0 : 1] &&
@@ -2190,7 +2190,7 @@ int Engine::run_batch(const std::vector<const PodSpec*>& pods, const std::vector
   // every workgroup's LDS lists must hold its nodes' pods and terms plus everything this batch can add
   // (each pod, and its own terms, at most once).  Every rank decides alike: the check covers every
   // rank's workgroups (each rank holds the whole cluster).
-  bool use_agg = loop_worth && !diag && (!comm || dx) && !eval && c->cfg.persistent_loop && c->cfg.agg_loop && NB > 0 && G >= 1 &&
+  bool use_agg = loop_worth && (!comm || dx) && !eval && c->cfg.persistent_loop && c->cfg.agg_loop && NB > 0 && G >= 1 &&
                  G * W <= std::min(cus, 256) && (int64_t)G * kLoopMaxBlk >= NBs &&
                  (int64_t)G * dev_ranks <= (int64_t)cus * loop_occ[W > 1 ? 3 : 2] &&
                  (int64_t)c->taint_max_per_node < ((int64_t)1 << 24) - 1;
@@ -2573,6 +2573,7 @@ int Engine::run_batch(const std::vector<const PodSpec*>& pods, const std::vector
       av.region = (unsigned long long*)d_region.p;
       av.fail = (uint32_t*)d_fail.p;
       av.desc_bytes = (const uint32_t*)d_off.p + n;
+      av.diag = diag ? (int32_t*)d_diag.p : nullptr;  // the diagnosing instance (launch_agg_loop): no k_diag_reduce
       // the template cache (aggLoopDebug bits 0 / 2: no folds / no same-template shortcut; bit 5: no cache)
       if (!comm && !ptss && !(c->cfg.agg_debug & (1 | 4 | 32))) {
         if (h_tcw_n < (size_t)n) {
