@@ -219,7 +219,12 @@ typedef struct ksg_diagnosis {
   int32_t reason_nodes[KSG_NUM_REASONS];    /* nodes whose status carries reason bit r: FitError.Error()'s histogram */
 } ksg_diagnosis;
 /* ksg_schedule_one / ksg_schedule_batch with the diagnosis of every cycle (diags[n]); results, assumes and every
- * side effect are those of the undiagnosed calls.  KSG_ENOTSUP on a node-sharded context. */
+ * side effect are those of the undiagnosed calls.
+ * On a node-sharded context: KSG_ENOTSUP, and nothing runs, unless the context was created with
+ * "distributed": {..., "diagnosis": true}.  With it both calls are collective across the W ranks, as ksg_schedule_one /
+ * ksg_schedule_batch are: every rank calls the same variant with the same pods (and the same eval request), and
+ * every rank returns the same results and the same complete, cluster-wide ksg_diagnosis per pod.  Each rank reduces
+ * the nodes of its own range; one all-reduce (sum) per call completes the rows on every rank. */
 int ksg_schedule_one_diag(ksg_ctx *ctx, int32_t handle, uint32_t flags, ksg_result *result, ksg_eval_out *eval /* may be NULL */,
                           ksg_diagnosis *diag);
 int ksg_schedule_batch_diag(ksg_ctx *ctx, const int32_t *handles, int32_t n, uint32_t flags, ksg_result *results,
@@ -343,6 +348,13 @@ int ksg_preempt(ksg_ctx *ctx, int32_t handle, const char *args_json, size_t args
  * AssumePod.  ksg_create is collective across the W ranks (ncclCommInitRank).  With
  * "localGroup": "<name>" instead of ncclId, W contexts in ONE process on one device form the
  * group (each driven by its own thread); used to test the sharded path on one GPU.
+ * "diagnosis": true inside "distributed" (default false) opts the context into ksg_schedule_one_diag /
+ * ksg_schedule_batch_diag as collective calls; without a transport (ncclId or localGroup) it is an invalid argument
+ * and ksg_create fails.  The value must be equal on every rank.  An in-process group checks that once, at its first
+ * diagnosed call, before anything is enqueued: ranks that disagree all return KSG_EINVAL and schedule nothing (a
+ * group none of whose ranks opted in refuses at once, without waiting for a peer).  RCCL ranks have no host channel
+ * to check it through: like the rest of the config it is the caller's contract, and ranks that disagree leave the
+ * opted-in ranks waiting in the collective.
  * ksg_comm_unique_id writes ncclGetUniqueId as 256 hex characters + NUL (rank 0 calls it and
  * hands it to the other ranks) and returns the length. */
 int ksg_comm_unique_id(char *buf, size_t cap);

@@ -1389,13 +1389,15 @@ __device__ __forceinline__ void diag_accumulate(uint32_t st, bool valid, int32_t
 // k_diag_reduce (node blocks, behind k_select on the stream): the launch path's reduction of the status words the
 // pod's node pass stored (DF_DIAG) into its row.  The pod's outcome is read on the device: anything but a FitError
 // (no feasible node) returns at once and leaves the row zero.
-__global__ __launch_bounds__(kBlock) void k_diag_reduce(MirrorView m, BatchView b, int pod, int32_t* rows) {
+// blk0: the first node block of the grid (node-sharded: behind k_commit, over the rank's own block range; the
+// outcome in b.results is the global one, so every rank takes the same branch and the ranks' rows add up).
+__global__ __launch_bounds__(kBlock) void k_diag_reduce(MirrorView m, BatchView b, int pod, int32_t* rows, int blk0) {
   __shared__ DiagLds s_dg;
   const DevResult& r = b.results[pod];
   if (r.feasible != 0 || (r.status != (int32_t)C_UNSCHED && r.status != (int32_t)C_UU)) return;  // workgroup-uniform
   if (threadIdx.x <= DG_BINS) reinterpret_cast<uint32_t*>(&s_dg)[threadIdx.x] = 0u;
   __syncthreads();
-  const int i = (int)blockIdx.x * kBlock + (int)threadIdx.x;
+  const int i = (blk0 + (int)blockIdx.x) * kBlock + (int)threadIdx.x;
   const bool valid = i < m.n;
   diag_accumulate(valid ? b.status[i] : 0u, valid, rows + (size_t)pod * kDiagWords, s_dg, kBlock / 64);
 }
@@ -2210,7 +2212,7 @@ __constant__ int8_t kSplitWaveMap[2][6] = {{0, 1, 2, 3, 4, 5}, {4, 5, 0, 1, 2, 3
 template <int NW, bool RING, int MS, bool GRP, bool NOM, bool SPLIT = false, bool DIAG = false>
 __device__ __forceinline__ void sched_loop_body(const MirrorView& m, const BatchView& b, const LoopView& lv, const int w_grp) {
   static_assert(!SPLIT || (NW == 2 && !RING && !GRP && !NOM), "the split instance: unsharded 128-node-unit batch runs");
-  static_assert(!DIAG || (!RING && !GRP), "the diagnosing instances: unsharded batch runs");
+  static_assert(!DIAG || !RING, "the diagnosing instances: batch runs");
   constexpr int U = NW * 64;                  // nodes per unit: one per evaluation-wave lane
   // NW evaluation waves, one selection wave, one helper wave (SPLIT: and NW post-evaluation waves)
   constexpr int kLoopThreads = U + 128 + (SPLIT ? U : 0);
@@ -3300,10 +3302,12 @@ __device__ __forceinline__ void apply_entry(const MirrorView& m, const uint8_t* 
 // workgroups holds a quarter of the exchange registers, which pays for the PodTopologySpread PX skip, as in RING)
 // DIAG: a diagnosed batch run (AggView::diag): phase 1's packed Filter statuses are held in LDS, and where a pod's
 // cycle ends without a feasible node wave 0 of every workgroup adds its nodes' statuses to the pod's row.
+// (SHARD / GRP: F is the count over all world * G participants, so every rank's workgroups take the branch; s_st
+// holds this workgroup's slots only -- 0 where it has no node -- and the row is this rank's own, summed on the host.)
 // (the body of k_agg_loop and k_agg_loop_group: w = the workgroup this block plays in its rank)
 template <bool SHARD, bool PTSS, bool RING, int MS, bool GRP, bool DIAG = false>
 __device__ __forceinline__ void agg_loop_body(const MirrorView& m, const BatchView& b, const AggView& av, const int w_grp) {
-  static_assert(!DIAG || (!RING && !SHARD && !GRP), "the diagnosing instances: unsharded batch runs");
+  static_assert(!DIAG || !RING, "the diagnosing instances: batch runs");
   constexpr bool kPxa = RING || MS < kMaxSweep;  // phase 1 guesses the PTS raw scores (AG_PXA)
   constexpr int kBlob = RING ? kBlobLds : kAggBlobLds;       // program slot bytes (desc.h)
   constexpr uint32_t kLp = RING ? kAggRingPods : kAggPods;     // LDS list entries (the rest spill to HBM)
@@ -5109,7 +5113,8 @@ __device__ __forceinline__ void agg_loop_body(const MirrorView& m, const BatchVi
     stamp(q, 8);
   }
 }
-// DIAG: the diagnosing instance (AggView::diag set): the twins of the four unsharded batch instances
+// DIAG: the diagnosing instance (AggView::diag set): the twins of the four unsharded batch instances and of the
+// node-sharded one
 template <bool SHARD, bool PTSS, bool RING = false, int MS = kMaxSweep, bool DIAG = false>
 __global__ __launch_bounds__(kAggThreads) void k_agg_loop(MirrorView m, BatchView b, AggView av) {
   const AggGroupArg& a = *(const AggGroupArg*)__builtin_amdgcn_kernarg_segment_ptr();  // (k_sched_loop)
@@ -5120,6 +5125,22 @@ __global__ __launch_bounds__(kAggThreads) void k_agg_loop_group(const AggGroupAr
   const int r = (int)blockIdx.x / G;
   const AggGroupArg& a = ga[r];
   agg_loop_body<true, true, false, kMaxSweep, true>(a.m, a.b, a.av, (int)blockIdx.x - r * G);
+}
+// The diagnosing group instances (a diagnosed call on an in-process group): every rank's argument
+// carries its own rows (LoopView::diag / AggView::diag), and each workgroup adds the nodes it owns to the rows of
+// the rank it plays.  Kernels of their own, so that the undiagnosed group kernels stay what they are; every sweep
+// round, as the unsplit diagnosing instances.
+template <int NW>
+__global__ __launch_bounds__(NW * 64 + 128) void k_sched_loop_group_diag(const LoopGroupArg* __restrict__ ga, int G) {
+  const int r = (int)blockIdx.x / G;
+  const LoopGroupArg& a = ga[r];
+  sched_loop_body<NW, false, kMaxSweep, true, false, false, true>(a.m, a.b, a.lv, (int)blockIdx.x - r * G);
+}
+template <bool PTSS>
+__global__ __launch_bounds__(kAggThreads) void k_agg_loop_group_diag(const AggGroupArg* __restrict__ ga, int G) {
+  const int r = (int)blockIdx.x / G;
+  const AggGroupArg& a = ga[r];
+  agg_loop_body<true, PTSS, false, kMaxSweep, true, true>(a.m, a.b, a.av, (int)blockIdx.x - r * G);
 }
 
 }  // namespace ksg
@@ -5162,10 +5183,11 @@ hipError_t launch_nominated(const MirrorView& m, const BatchView& b, int pod, hi
   hipLaunchKernelGGL(k_nominated, dim3(1), dim3(64), 0, s, m, b, pod);
   return hipGetLastError();
 }
-hipError_t launch_diag_reduce(const MirrorView& m, const BatchView& b, int pod, int32_t* rows, hipStream_t s) {
-  const int nb = (m.n + kBlock - 1) / kBlock;
-  if (nb == 0) return hipSuccess;
-  hipLaunchKernelGGL(k_diag_reduce, dim3(nb), dim3(kBlock), 0, s, m, b, pod, rows);
+hipError_t launch_diag_reduce(const MirrorView& m, const BatchView& b, int pod, int32_t* rows, hipStream_t s, int blk0,
+                              int nblk) {
+  const int nb = nblk < 0 ? (m.n + kBlock - 1) / kBlock : nblk;  // (nblk < 0: all of them)
+  if (nb == 0) return hipSuccess;  // no node, or an empty shard
+  hipLaunchKernelGGL(k_diag_reduce, dim3(nb), dim3(kBlock), 0, s, m, b, pod, rows, blk0);
   return hipGetLastError();
 }
 hipError_t launch_ob_store(const BatchView& b, int pod, hipStream_t s) {
@@ -5422,8 +5444,14 @@ hipError_t launch_put_group_arg(const AggGroupArg& a, AggGroupArg* dst, hipStrea
 }
 // In-process rank groups: every rank's loop in one dispatch of world * nwg workgroups (ga: [world] in device
 // memory; the same instance choice as launch_sched_loop / launch_agg_loop's node-sharded batch instances)
+// (diag: the leader's LoopView::diag / AggView::diag is set -- the diagnosing instances, defined last)
+static hipError_t launch_sched_loop_group_diag(const LoopGroupArg* ga, int world, int nwg, hipStream_t s, hipEvent_t t0,
+                                               hipEvent_t t1, int unit);
+static hipError_t launch_agg_loop_group_diag(const AggGroupArg* ga, int world, int nwg, hipStream_t s, hipEvent_t t0,
+                                             hipEvent_t t1);
 hipError_t launch_sched_loop_group(const LoopGroupArg* ga, int world, int nwg, hipStream_t s, hipEvent_t t0,
-                                   hipEvent_t t1, int unit) {
+                                   hipEvent_t t1, int unit, bool diag) {
+  if (diag) return launch_sched_loop_group_diag(ga, world, nwg, s, t0, t1, unit);
   const dim3 grid(world * nwg);
   if (unit == 128 && world * nwg <= 64)
     hipExtLaunchKernelGGL((k_sched_loop_group<2, 1>), grid, dim3(2 * 64 + 128), 0, s, t0, t1, 0, ga, nwg);
@@ -5433,7 +5461,9 @@ hipError_t launch_sched_loop_group(const LoopGroupArg* ga, int world, int nwg, h
     hipExtLaunchKernelGGL((k_sched_loop_group<4, kMaxSweep>), grid, dim3(kLoopThreads), 0, s, t0, t1, 0, ga, nwg);
   return hipGetLastError();
 }
-hipError_t launch_agg_loop_group(const AggGroupArg* ga, int world, int nwg, hipStream_t s, hipEvent_t t0, hipEvent_t t1) {
+hipError_t launch_agg_loop_group(const AggGroupArg* ga, int world, int nwg, hipStream_t s, hipEvent_t t0, hipEvent_t t1,
+                                 bool diag) {
+  if (diag) return launch_agg_loop_group_diag(ga, world, nwg, s, t0, t1);
   hipExtLaunchKernelGGL(k_agg_loop_group, dim3(world * nwg), dim3(kAggThreads), 0, s, t0, t1, 0, ga, nwg);
   return hipGetLastError();
 }
@@ -5478,10 +5508,23 @@ hipError_t loop_occupancy(int (&occ)[4]) {
     if (e != hipSuccess) return e;
     occ[2] = o < occ[2] ? o : occ[2];
   }
+  // (the diagnosing node-sharded instances: k_sched_loop_group's by unit, k_agg_loop's sharded and group ones)
+  const K kd[4] = {{reinterpret_cast<const void*>(&k_sched_loop_group_diag<2>), 2 * 64 + 128},
+                   {reinterpret_cast<const void*>(&k_sched_loop_group_diag<4>), kLoopThreads},
+                   {reinterpret_cast<const void*>(&k_agg_loop<true, true, false, kMaxSweep, true>), kAggThreads},
+                   {reinterpret_cast<const void*>(&k_agg_loop_group_diag<true>), kAggThreads}};
+  for (int i = 0; i < 4; ++i) {
+    int o = 0;
+    const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&o, kd[i].f, kd[i].threads, 0);
+    if (e != hipSuccess) return e;
+    const int k = i < 2 ? i : 3;
+    occ[k] = o < occ[k] ? o : occ[k];
+  }
   return hipSuccess;
 }
 // Loads the module's code object onto the current device now (hipFuncGetAttributes), so that no
 // first launch inside a batch does it while an in-process peer's persistent loop is running.
+__global__ __launch_bounds__(kBlock) void k_sum_reduce(int32_t* __restrict__ dst, RankPtrs src, int nsrc, size_t count);
 hipError_t warm_kernels() {
   hipFuncAttributes a;
   const void* fs[] = {reinterpret_cast<const void*>(&k_filter_score<true>), reinterpret_cast<const void*>(&k_filter_score<false>),
@@ -5523,14 +5566,21 @@ hipError_t warm_kernels() {
                       reinterpret_cast<const void*>(&k_agg_loop<false, true, false, 1, true>),
                       reinterpret_cast<const void*>(&k_agg_loop<false, true, false, kMaxSweep, true>),
                       reinterpret_cast<const void*>(&k_agg_loop<false, false, false, 1, true>),
-                      reinterpret_cast<const void*>(&k_agg_loop<false, false, false, kMaxSweep, true>)};
+                      reinterpret_cast<const void*>(&k_agg_loop<false, false, false, kMaxSweep, true>),
+                      reinterpret_cast<const void*>(&k_sched_loop_group_diag<2>),
+                      reinterpret_cast<const void*>(&k_sched_loop_group_diag<4>),
+                      reinterpret_cast<const void*>(&k_agg_loop<true, true, false, kMaxSweep, true>),
+                      reinterpret_cast<const void*>(&k_agg_loop_group_diag<true>),
+                      reinterpret_cast<const void*>(&k_sum_reduce)};
   for (const void* f : fs) {
     const hipError_t e = hipFuncGetAttributes(&a, f);
     if (e != hipSuccess) return e;
   }
   return hipSuccess;
 }
-// A diagnosed batch run (LoopView::diag; unsharded, never resident): k_sched_loop's diagnosing instances.
+// A diagnosed batch run (LoopView::diag; never resident): k_sched_loop's diagnosing instances.  Node-sharded RCCL
+// ranks (lv.world > 1) run the unsplit ones: every workgroup adds the nodes it owns to this rank's rows, the pod's
+// result is committed on every rank (F is exchange A's global count), and the host sums the ranks' rows.
 static hipError_t launch_sched_loop_diag(const MirrorView& m, const BatchView& b, const LoopView& lv, hipStream_t s,
                                          hipEvent_t t0, hipEvent_t t1, int unit) {
   const dim3 grid(lv.nwg);
@@ -5544,21 +5594,35 @@ static hipError_t launch_sched_loop_diag(const MirrorView& m, const BatchView& b
   }
   return hipGetLastError();
 }
-// A diagnosed batch run (AggView::diag; unsharded, never resident): k_agg_loop's diagnosing instances, chosen as
-// launch_agg_loop chooses among the unsharded batch instances.
+// A diagnosed batch run (AggView::diag; never resident): k_agg_loop's diagnosing instances, chosen as launch_agg_loop
+// chooses among the batch instances (node-sharded RCCL ranks: the sharded PTSS one, this rank's rows).
 static hipError_t launch_agg_loop_diag(const MirrorView& m, const BatchView& b, const AggView& av, hipStream_t s,
                                        hipEvent_t t0, hipEvent_t t1) {
-  if (av.ring != nullptr || av.world > 1) return hipErrorInvalidValue;
+  if (av.ring != nullptr) return hipErrorInvalidValue;
   auto go = [&](auto kern) {
     if (t0)
       hipExtLaunchKernelGGL(kern, dim3(av.nwg), dim3(kAggThreads), 0, s, t0, t1, 0, m, b, av);
     else
       hipLaunchKernelGGL(kern, dim3(av.nwg), dim3(kAggThreads), 0, s, m, b, av);
   };
-  if (av.ptss && av.nwg <= 64) go(k_agg_loop<false, true, false, 1, true>);
+  if (av.world > 1) go(k_agg_loop<true, true, false, kMaxSweep, true>);  // node-sharded (RCCL ranks): the PTSS one, as launch_agg_loop
+  else if (av.ptss && av.nwg <= 64) go(k_agg_loop<false, true, false, 1, true>);
   else if (av.ptss) go(k_agg_loop<false, true, false, kMaxSweep, true>);
   else if (av.nwg <= 64) go(k_agg_loop<false, false, false, 1, true>);
   else go(k_agg_loop<false, false, false, kMaxSweep, true>);
+  return hipGetLastError();
+}
+// A diagnosed call on an in-process group: the diagnosing group instances (every sweep round).
+static hipError_t launch_sched_loop_group_diag(const LoopGroupArg* ga, int world, int nwg, hipStream_t s, hipEvent_t t0,
+                                               hipEvent_t t1, int unit) {
+  const dim3 grid(world * nwg);
+  if (unit == 128) hipExtLaunchKernelGGL((k_sched_loop_group_diag<2>), grid, dim3(2 * 64 + 128), 0, s, t0, t1, 0, ga, nwg);
+  else hipExtLaunchKernelGGL((k_sched_loop_group_diag<4>), grid, dim3(kLoopThreads), 0, s, t0, t1, 0, ga, nwg);
+  return hipGetLastError();
+}
+static hipError_t launch_agg_loop_group_diag(const AggGroupArg* ga, int world, int nwg, hipStream_t s, hipEvent_t t0,
+                                             hipEvent_t t1) {
+  hipExtLaunchKernelGGL((k_agg_loop_group_diag<true>), dim3(world * nwg), dim3(kAggThreads), 0, s, t0, t1, 0, ga, nwg);
   return hipGetLastError();
 }
 #ifdef KSG_DIAG
@@ -6420,6 +6484,23 @@ __global__ __launch_bounds__(kBlock) void k_eval_pack(BatchView b, int n, int ca
 hipError_t launch_eval_pack(const BatchView& b, int n, int cap, int lo, int hi, unsigned long long* g, hipStream_t s) {
   if (hi <= lo) return hipSuccess;
   hipLaunchKernelGGL(k_eval_pack, dim3((hi - lo + kBlock - 1) / kBlock), dim3(kBlock), 0, s, b, n, cap, lo, hi, g);
+  return hipGetLastError();
+}
+
+// (defined last: the kernels before it lie in the code object where they lay without it)
+// k_sum_reduce: the in-process all-reduce(SUM) of the local communicator (the diagnosis rows): dst[w] = the sum over
+// the ranks' vectors.  Not in place: every rank's kernel reads every rank's src, so dst is a buffer no peer reads.
+__global__ __launch_bounds__(kBlock) void k_sum_reduce(int32_t* __restrict__ dst, RankPtrs src, int nsrc, size_t count) {
+  for (size_t w = (size_t)blockIdx.x * kBlock + threadIdx.x; w < count; w += (size_t)gridDim.x * kBlock) {
+    int32_t v = 0;
+    for (int r = 0; r < nsrc; ++r) v += reinterpret_cast<const int32_t*>(src.p[r])[w];
+    dst[w] = v;
+  }
+}
+hipError_t launch_sum_reduce(int32_t* dst, const RankPtrs& src, int nsrc, size_t count, hipStream_t s) {
+  const size_t nb = (count + kBlock - 1) / kBlock;
+  hipLaunchKernelGGL(k_sum_reduce, dim3(nb < 64 ? (nb > 0 ? (unsigned)nb : 1u) : 64u), dim3(kBlock), 0, s, dst, src, nsrc,
+                     count);
   return hipGetLastError();
 }
 

@@ -257,11 +257,39 @@ int ksg_pod_release(ksg_ctx* ctx, int32_t handle) {
   return ctx->engine->queue.erase(handle) ? KSG_OK : KSG_ENOTFOUND;
 }
 
-// a node-sharded context has no diagnosed cycles (the rows are reduced on one device's mirror)
+// A node-sharded context diagnoses only where it was created with distributed.diagnosis true: the
+// calls are then collective, each rank reducing its own shard's rows, summed over the ranks.  Without it they are
+// refused and run nothing.  The value must be the same on every rank.  An in-process group checks that here, once,
+// at its first diagnosed call, before anything is enqueued (Comm::agree): a rank without the opt-in joins that check
+// only when some member of its group has it -- a group none of whose members opted in never waits for a peer.
+// RCCL ranks have no host channel: the caller's contract, as the rest of the config.
 static int diag_refused(ksg_ctx* ctx) {
-  if (!ctx->engine->comm) return KSG_OK;
-  ctx->err = "ksg_schedule_one_diag / ksg_schedule_batch_diag on a node-sharded context";
-  return KSG_ENOTSUP;
+  Engine& e = *ctx->engine;
+  if (!e.comm) return KSG_OK;
+  const bool mine = ctx->cluster->cfg.shard_diagnosis;
+  const auto refuse = [&]() {
+    ctx->err = "ksg_schedule_one_diag / ksg_schedule_batch_diag on a node-sharded context";
+    return KSG_ENOTSUP;
+  };
+  if (!e.comm->in_process()) return mine ? KSG_OK : refuse();
+  if (e.diag_agreed_) return KSG_OK;
+  if (!mine && !e.comm->diagnosis_opted_in()) return refuse();
+  std::vector<int64_t> all;
+  if (e.comm->agree(mine ? 1 : 0, &all) != KSG_OK) {
+    ctx->err = e.comm->err;
+    return KSG_EDEVICE;
+  }
+  bool same = true;
+  for (int64_t v : all) same = same && v == all[0];
+  if (!same) {
+    std::string o;
+    for (size_t r = 0; r < all.size(); ++r) o += (r ? ", rank " : "rank ") + std::to_string(r) + ": " + (all[r] ? "true" : "false");
+    ctx->err = "distributed.diagnosis differs between the ranks of the group (" + o + "): nothing was scheduled";
+    return KSG_EINVAL;
+  }
+  if (!mine) return refuse();
+  e.diag_agreed_ = true;
+  return KSG_OK;
 }
 
 // ksg_schedule_one (diag == NULL) / ksg_schedule_one_diag.  A diagnosed cycle takes the launch path: its status

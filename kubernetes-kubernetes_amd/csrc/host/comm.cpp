@@ -18,6 +18,7 @@
 namespace ksg {
 
 hipError_t launch_max_reduce(unsigned long long* dst, const RankPtrs& src, int nsrc, int count, hipStream_t s);
+hipError_t launch_sum_reduce(int32_t* dst, const RankPtrs& src, int nsrc, size_t count, hipStream_t s);
 
 // ---------------------------------------------------------------------------------------------
 // RCCL: one process per GPU (bench.py under torch.distributed.run); ncclMax over uint64.
@@ -29,6 +30,14 @@ class RcclComm : public Comm {
     const ncclResult_t r = ncclAllReduce(buf, buf, count, ncclUint64, ncclMax, comm, s);
     if (r != ncclSuccess) {
       err = std::string("ncclAllReduce: ") + ncclGetErrorString(r);
+      return KSG_EDEVICE;
+    }
+    return KSG_OK;
+  }
+  int all_reduce_sum_i32(const int32_t* src, int32_t* dst, size_t count, hipStream_t s) override {
+    const ncclResult_t r = ncclAllReduce(src, dst, count, ncclInt32, ncclSum, comm, s);
+    if (r != ncclSuccess) {
+      err = std::string("ncclAllReduce (sum): ") + ncclGetErrorString(r);
       return KSG_EDEVICE;
     }
     return KSG_OK;
@@ -123,6 +132,7 @@ struct LocalGroup {
   std::mutex mu;
   std::condition_variable cv;
   int world = 0, arrived = 0, members = 0;
+  bool diagnosis = false;  // a member was created with distributed.diagnosis true (g_groups_mu)
   uint64_t gen = 0;
   hipEvent_t launched = nullptr;  // group_launch: the leader's event after the group's dispatch
   int launch_rc = 0;              // ... and the leader's status
@@ -203,6 +213,46 @@ class LocalComm : public Comm {
       return KSG_EDEVICE;
     }
     return KSG_OK;
+  }
+
+  // The sum of every rank's vector: the same event + rendezvous scheme.  Each rank's reduce kernel reads every
+  // rank's src and writes its own dst; a sum is not idempotent, so dst must be a buffer no peer reads (a peer
+  // that has not run its reduce yet would add the result instead of the share).  The srcs stay as they are until
+  // the batch-end rendezvous, which follows every rank's stream synchronisation.
+  int all_reduce_sum_i32(const int32_t* src, int32_t* dst, size_t count, hipStream_t s) override {
+    if (src == dst) {
+      err = "local exchange: the sum's destination must not be its source";
+      return KSG_EDEVICE;
+    }
+    hipEvent_t ev = ring[next_ev];
+    next_ev = (next_ev + 1) % kRing;
+    if (hipEventRecord(ev, s) != hipSuccess) {
+      err = "local exchange: hipEventRecord failed";
+      return KSG_EDEVICE;
+    }
+    int sl = 0;
+    if (!rendezvous(reinterpret_cast<unsigned long long*>(const_cast<int32_t*>(src)), ev, count, &sl)) {
+      err = "local exchange: ranks did not issue the same exchange sequence (timeout or size mismatch)";
+      return KSG_EDEVICE;
+    }
+    RankPtrs srcs{};
+    for (int r = 0; r < world; ++r) {
+      srcs.p[r] = g->snap_bufs[sl][r];
+      if (r != rank && hipStreamWaitEvent(s, g->snap_evs[sl][r], 0) != hipSuccess) {
+        err = "local exchange: hipStreamWaitEvent failed";
+        return KSG_EDEVICE;
+      }
+    }
+    if (launch_sum_reduce(dst, srcs, world, count, s) != hipSuccess) {
+      err = "local exchange: reduce launch failed";
+      return KSG_EDEVICE;
+    }
+    return KSG_OK;
+  }
+
+  bool diagnosis_opted_in() const override {
+    std::lock_guard<std::mutex> lk(g_groups_mu);
+    return g && g->diagnosis;
   }
 
   int share_buffers(void* mine, std::vector<void*>* all) override {  // one process: the pointers themselves
@@ -346,6 +396,7 @@ std::unique_ptr<Comm> make_comm(const Config& cfg, std::string* err) {
       return nullptr;
     }
     ++g->members;
+    g->diagnosis = g->diagnosis || cfg.shard_diagnosis;
     c->g = g;
   }
   return c;

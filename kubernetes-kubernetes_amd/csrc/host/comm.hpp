@@ -30,6 +30,13 @@ class Comm {
   int world = 1, rank = 0;
   // in-stream all-reduce(MAX) of `count` uint64 words at device pointer `buf`, in place
   virtual int all_reduce_max(unsigned long long* buf, size_t count, hipStream_t s) = 0;
+  // in-stream all-reduce(SUM) of `count` int32 words, src -> dst on every rank (the FitError diagnosis rows of a
+  // diagnosed sharded call).  src == dst is allowed over RCCL; the in-process transport needs a dst
+  // that no peer reads (its reduce kernel reads every rank's src while the peers' kernels write their dst)
+  virtual int all_reduce_sum_i32(const int32_t* src, int32_t* dst, size_t count, hipStream_t s) = 0;
+  // in-process groups: some member of the group was created with distributed.diagnosis true (RCCL ranks have no
+  // host channel: false)
+  virtual bool diagnosis_opted_in() const { return false; }
   // brackets several all-reduces that may be fused (ncclGroupStart/End)
   virtual int group_begin() { return 0; }
   virtual int group_end() { return 0; }

@@ -72,14 +72,16 @@ hipError_t launch_agg_loop(const MirrorView& m, const BatchView& b, const AggVie
 hipError_t launch_put_group_arg(const LoopGroupArg& a, LoopGroupArg* dst, hipStream_t s);
 hipError_t launch_put_group_arg(const AggGroupArg& a, AggGroupArg* dst, hipStream_t s);
 hipError_t launch_sched_loop_group(const LoopGroupArg* ga, int world, int nwg, hipStream_t s, hipEvent_t t0,
-                                   hipEvent_t t1, int unit);
-hipError_t launch_agg_loop_group(const AggGroupArg* ga, int world, int nwg, hipStream_t s, hipEvent_t t0, hipEvent_t t1);
+                                   hipEvent_t t1, int unit, bool diag);
+hipError_t launch_agg_loop_group(const AggGroupArg* ga, int world, int nwg, hipStream_t s, hipEvent_t t0, hipEvent_t t1,
+                                 bool diag);
 hipError_t warm_kernels();
 hipError_t warm_aggregate();
 hipError_t launch_ob_hint(const MirrorView& m, const BatchView& b, int pod, hipStream_t s);
 hipError_t launch_nominated(const MirrorView& m, const BatchView& b, int pod, hipStream_t s);
 hipError_t launch_ob_store(const BatchView& b, int pod, hipStream_t s);
-hipError_t launch_diag_reduce(const MirrorView& m, const BatchView& b, int pod, int32_t* rows, hipStream_t s);
+hipError_t launch_diag_reduce(const MirrorView& m, const BatchView& b, int pod, int32_t* rows, hipStream_t s, int blk0 = 0,
+                              int nblk = -1);
 hipError_t launch_ob_remap(ObState* st, ObEnt* h, const int32_t* map, int nold, int maxlen, hipStream_t s);
 hipError_t loop_occupancy(int (&occ)[4]);
 
@@ -1259,7 +1261,7 @@ Engine::~Engine() {
   for (DevBuf* b : {&d_descs, &d_meta, &d_status, &d_fmask, &d_blk, &d_fixed, &d_raw, &d_out,
                     &d_total, &d_arena, &d_xa, &d_xp, &d_xb, &d_xs, &d_gran, &d_fail, &d_grp, &d_agran, &d_region, &d_astamps, &d_aspill, &d_relay,
                     &d_evg, &d_aggpeers, &d_pre, &d_seg, &d_segcnt, &d_psout, &d_pdb, &d_pick, &d_contrib_buf, &d_wide, &d_vsc,
-                    &d_ob, &d_ob_heap, &d_ob_map, &d_tcache, &d_tcw, &d_nom, &d_diag})
+                    &d_ob, &d_ob_heap, &d_ob_map, &d_tcache, &d_tcw, &d_nom, &d_diag, &d_diag_sum})
     if (b->p) (void)hipFree(b->p);
   if (h_pinned) (void)hipHostFree(h_pinned);
   if (h_tcw) (void)hipHostFree(h_tcw);
@@ -1637,8 +1639,11 @@ int Engine::group_launch(GroupReq* req, bool agg, int nwg, int unit) {
         return KSG_EDEVICE;
     for (int r = 1; r < W; ++r)
       if (rq(r).t0 && hipEventRecord(rq(r).t0, ls) != hipSuccess) return KSG_EDEVICE;
-    const hipError_t e = agg ? launch_agg_loop_group((const AggGroupArg*)grp, W, nwg, ls, rq(0).t0, rq(0).t1)
-                             : launch_sched_loop_group((const LoopGroupArg*)grp, W, nwg, ls, rq(0).t0, rq(0).t1, unit);
+    // (a diagnosed call: the leader's view says so -- every rank of the call carries its own rows)
+    const hipError_t e =
+        agg ? launch_agg_loop_group((const AggGroupArg*)grp, W, nwg, ls, rq(0).t0, rq(0).t1, rq(0).aa.av.diag != nullptr)
+            : launch_sched_loop_group((const LoopGroupArg*)grp, W, nwg, ls, rq(0).t0, rq(0).t1, unit,
+                                      rq(0).la.lv.diag != nullptr);
     if (e != hipSuccess) return KSG_EDEVICE;
     for (int r = 1; r < W; ++r)
       if (rq(r).t1 && hipEventRecord(rq(r).t1, ls) != hipSuccess) return KSG_EDEVICE;
@@ -1851,7 +1856,9 @@ int Engine::run_batch_api(const std::vector<const PodSpec*>& pods, const std::ve
   const std::vector<int32_t> rh(handles.begin() + f, handles.end());
   force_allreduce_ = true;
   fault_first_ = -1;
-  const int r2 = run_batch(rest, rh, assume, results + f, nullptr);
+  // (a diagnosed call: the re-run is a call of its own over pods [f, n) -- it zeroes its rows, which the loop that
+  // gave up may have added to, and fills diag[f..n); the pods before f keep the diagnosis loop_fault gave them)
+  const int r2 = run_batch(rest, rh, assume, results + f, nullptr, diag ? diag + f : nullptr);
   force_allreduce_ = false;
   if (r2 == KSG_OK) {
     ++loop_retries_;
@@ -1865,10 +1872,13 @@ int Engine::run_batch(const std::vector<const PodSpec*>& pods, const std::vector
   const int n = (int)pods.size();
   if (n == 0) return KSG_OK;
   if (eval && n != 1) return KSG_EINVAL;
-  if (diag && comm) {
+  if (diag && comm && !c->cfg.shard_diagnosis) {  // not opted in (distributed.diagnosis): nothing runs
     c->err = "FitError diagnosis on a node-sharded context";
     return KSG_ENOTSUP;
   }
+  // A diagnosed sharded call: each rank's kernels add the nodes of its own shard to its own rows,
+  // one all-reduce (SUM) after the call's last kernel completes them on every rank, and only then are they read.
+  const bool sdiag = diag && comm;
   if (diag) std::memset(diag, 0, (size_t)n * sizeof(ksg_diagnosis));
   struct NomReset {
     bool* f;
@@ -2263,6 +2273,7 @@ int Engine::run_batch(const std::vector<const PodSpec*>& pods, const std::vector
       HIPCHK(hipHostMalloc((void**)&h_diag, (size_t)n * 2 * kDiagWords * 4, hipHostMallocDefault));
       h_diag_rows = (size_t)n * 2;
     }
+    if (sdiag && (rc = ensure(d_diag_sum, (size_t)n * kDiagWords * 4))) return rc;
   }
   struct Chunk { int a, b; };
   std::vector<Chunk> chunks;
@@ -2283,11 +2294,42 @@ int Engine::run_batch(const std::vector<const PodSpec*>& pods, const std::vector
     HIPCHK(hipMemcpyAsync(hr + a, (DevResult*)d_results.p + a, (size_t)(upto - a) * sizeof(DevResult),
                           hipMemcpyDeviceToHost, ds));
     if (use_loop || use_agg) HIPCHK(hipMemcpyAsync(hfail + chunks.size(), d_fail.p, 4, hipMemcpyDeviceToHost, ds));
-    if (diag)  // the chunk's rows, in the same step as its results
+    if (diag && !sdiag)  // the chunk's rows, in the same step as its results (sharded: after the sum)
       HIPCHK(hipMemcpyAsync(h_diag + (size_t)a * kDiagWords, (int32_t*)d_diag.p + (size_t)a * kDiagWords,
                             (size_t)(upto - a) * kDiagWords * 4, hipMemcpyDeviceToHost, ds));
     HIPCHK(hipEventRecord(cev[chunks.size()], ds));
     chunks.push_back({a, upto});
+    return KSG_OK;
+  };
+  // the diagnosis of pod i from its row, once its result is final (every counter 0 unless a FitError)
+  auto diagnose = [&](int i) {
+    ksg_diagnosis& g = diag[i];
+    g.num_nodes = m.n;
+    g.prefilter_code = cp[i].prefilter_reject ? cp[i].prefilter_code : 0;
+    g.prefilter_plugin = cp[i].prefilter_reject ? cp[i].prefilter_plugin : KSG_PLUGIN_NONE;
+    const int32_t st = results[i].status;
+    if (cp[i].error || (st != KSG_CODE_UNSCHEDULABLE && st != KSG_CODE_UNSCHEDULABLE_AND_UNRESOLVABLE)) return;
+    const int32_t* row = h_diag + (size_t)i * kDiagWords;
+    g.failed_nodes = row[DG_FAILED];
+    g.unresolvable_nodes = row[DG_UNRES];
+    for (int q = 0; q < kNumPlugins; ++q) {
+      g.plugin_nodes[q] = row[DG_PLUGIN + q];
+      if (row[DG_PLUGIN + q] > 0) g.unschedulable_plugins |= 1u << q;
+    }
+    for (int q = 0; q < kNumReasons; ++q) g.reason_nodes[q] = row[DG_REASON + q];
+  };
+  // A diagnosed sharded call: the cross-rank sum of the rows and their D2H copy, once per call -- after the call's
+  // last kernel (or from loop_fault, for the pods before a give-up), never per pod.  One sum and not one per chunk:
+  // a chunk is also closed where a rank's staging buffers had to grow, which the ranks need not decide alike.
+  bool rows_summed = false;
+  auto sum_rows = [&]() -> int {
+    if (!sdiag || rows_summed) return KSG_OK;
+    rows_summed = true;
+    if (comm->all_reduce_sum_i32((const int32_t*)d_diag.p, (int32_t*)d_diag_sum.p, (size_t)n * kDiagWords, s)) {
+      c->err = comm->err;
+      return KSG_EDEVICE;
+    }
+    HIPCHK(hipMemcpyAsync(h_diag, d_diag_sum.p, (size_t)n * kDiagWords * 4, hipMemcpyDeviceToHost, s));
     return KSG_OK;
   };
   // results + host shadow of the device-side assumes for pods [a, b)
@@ -2298,23 +2340,6 @@ int Engine::run_batch(const std::vector<const PodSpec*>& pods, const std::vector
       double* t; clk::time_point s;
       ~Acc() { *t += std::chrono::duration<double, std::micro>(clk::now() - s).count(); }
     } acc_{&settle_us, Ts};
-    // the diagnosis of pod i from its row, once its result is final (every counter 0 unless a FitError)
-    auto diagnose = [&](int i) {
-      ksg_diagnosis& g = diag[i];
-      g.num_nodes = m.n;
-      g.prefilter_code = cp[i].prefilter_reject ? cp[i].prefilter_code : 0;
-      g.prefilter_plugin = cp[i].prefilter_reject ? cp[i].prefilter_plugin : KSG_PLUGIN_NONE;
-      const int32_t st = results[i].status;
-      if (cp[i].error || (st != KSG_CODE_UNSCHEDULABLE && st != KSG_CODE_UNSCHEDULABLE_AND_UNRESOLVABLE)) return;
-      const int32_t* row = h_diag + (size_t)i * kDiagWords;
-      g.failed_nodes = row[DG_FAILED];
-      g.unresolvable_nodes = row[DG_UNRES];
-      for (int q = 0; q < kNumPlugins; ++q) {
-        g.plugin_nodes[q] = row[DG_PLUGIN + q];
-        if (row[DG_PLUGIN + q] > 0) g.unschedulable_plugins |= 1u << q;
-      }
-      for (int q = 0; q < kNumReasons; ++q) g.reason_nodes[q] = row[DG_REASON + q];
-    };
     for (int i = a; i < b; ++i) {
       ksg_result& r = results[i];
       if (cp[i].error) {
@@ -2354,7 +2379,7 @@ int Engine::run_batch(const std::vector<const PodSpec*>& pods, const std::vector
         c->pod_table_drop(cp[i].slot);  // not placed: the reserved pod-table slot never went live
       }
     }
-    for (int i = a; i < b && diag; ++i) diagnose(i);
+    for (int i = a; i < b && diag && !sdiag; ++i) diagnose(i);  // (sharded: after the sum, at the call's end)
     return KSG_OK;
   };
   // A persistent loop gave up (a workgroup never reached an exchange): pods [first, n) are not
@@ -2362,8 +2387,12 @@ int Engine::run_batch(const std::vector<const PodSpec*>& pods, const std::vector
   // rewound to before them -- and the device mirror, which may hold some of their assumes, is
   // rebuilt from the cache shadow at the next cycle.  The context stays usable.
   auto loop_fault = [&](int first, const std::string& why) -> int {
+    // (a diagnosed sharded call: the pods before `first` are scheduled and keep their diagnosis, which needs the
+    // sum -- every rank gives up at the same pod, or the group is out of step and the sum fails as the retry would)
+    const bool summed = sdiag && first > 0 && sum_rows() == KSG_OK;
     (void)hipStreamSynchronize(s);
     if (cstream) (void)hipStreamSynchronize(cstream);
+    for (int j = 0; j < first && j < n && summed; ++j) diagnose(j);
     for (int j = first; j < n; ++j) {
       results[j] = ksg_result{KSG_CODE_ERROR, -1, 0, 0, 0};
       c->pod_table_drop(j < compiled ? cp[j].slot : (pre_slot.empty() ? -1 : pre_slot[j]));
@@ -2652,6 +2681,7 @@ int Engine::run_batch(const std::vector<const PodSpec*>& pods, const std::vector
   HIPCHK(hipEventRecord(ev1, s));
   const auto T2 = clk::now();
   if ((rc = close_chunk(n))) return rc;
+  if ((rc = sum_rows())) return rc;  // behind the call's last kernel; the stream synchronisation below covers its copy
   std::vector<uint32_t> st;
   std::vector<int64_t> outs, tot;
   std::vector<unsigned long long> gath;
@@ -2994,6 +3024,7 @@ int Engine::run_batch(const std::vector<const PodSpec*>& pods, const std::vector
   // ---- results + host shadow of the device-side assumes
   if (chunks.size() <= 1 && settled == 0)
     if ((rc = settle(0, n))) return rc;
+  for (int i = 0; i < n && sdiag; ++i) diagnose(i);  // every result is final, the summed rows have landed
   if (c->cfg.loop_stamps) {
     const auto T4 = clk::now();
     auto us = [](clk::time_point a, clk::time_point b) { return std::chrono::duration<double, std::micro>(b - a).count(); };
@@ -3127,6 +3158,9 @@ int Engine::run_sharded(const std::vector<CompiledPod>& cp, const BatchView& bv,
     HIPCHK(launch_select_shard(m, bv, sv, i, s));
     if ((rc = xchg(sv.xb + (size_t)i * XB_WORDS, XB_WORDS))) return rc;
     HIPCHK(launch_commit(m, bv, sv, i, s));
+    // a diagnosed call: this rank's share of the pod's row, over its own blocks (none for an empty shard); k_commit
+    // left the global outcome in the pod's result, so every rank reduces or none does
+    if (hd.flags & DF_DIAG) HIPCHK(launch_diag_reduce(m, bv, i, (int32_t*)d_diag.p, s, sv.blk0, sv.nblk));
     *bytes += algo_bytes(hd) * frac;
     (*launches)++;
   }

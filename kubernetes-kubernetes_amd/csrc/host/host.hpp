@@ -249,6 +249,9 @@ struct Config {
   // out of `world`; the per-pod exchanges run over RCCL (nccl_id) or in-process (local_group)
   int world = 1, rank = 0;
   std::string nccl_id, local_group;
+  // distributed.diagnosis: ksg_schedule_*_diag are collective calls on this sharded context;
+  // off (the default): they are refused
+  bool shard_diagnosis = false;
   // a transport was configured: run the node-sharded pipeline even at worldSize 1 (tests it alone)
   bool sharded() const { return world > 1 || !nccl_id.empty() || !local_group.empty(); }
   Config();
@@ -585,7 +588,7 @@ class Engine {
                        uint32_t* smask, CompiledPod* out);
   // run a batch of cycles (device-resident, sequential semantics)
   // diag (ksg_schedule_*_diag, [pods]): every pod's FitError diagnosis as of its own cycle, reduced on the device
-  // (DESIGN.md §4.11); unsharded contexts only
+  // (DESIGN.md §4.11); a node-sharded context: collective, with distributed.diagnosis (§6)
   int run_batch(const std::vector<const PodSpec*>& pods, const std::vector<int32_t>& handles, bool assume,
                 ksg_result* results, ksg_eval_out* eval, ksg_diagnosis* diag = nullptr);
   // run_batch, and for an in-process rank group whose persistent loop gave up (its ranks' loops could not all
@@ -593,7 +596,8 @@ class Engine {
   // failed chunk on once more over the all-reduce path
   int run_batch_api(const std::vector<const PodSpec*>& pods, const std::vector<int32_t>& handles, bool assume,
                     ksg_result* results, ksg_eval_out* eval, ksg_diagnosis* diag = nullptr);
-  int fault_first_ = -1;        // the first pod loop_fault left unscheduled (-1: none), for run_batch_api
+  bool diag_agreed_ = false;    // in-process group: every rank has distributed.diagnosis (checked at the first diagnosed call)
+  int fault_first_ = -1;      // the first pod loop_fault left unscheduled (-1: none), for run_batch_api
   bool force_allreduce_ = false;  // run_batch_api's retry: no device exchange
   uint64_t loop_retries_ = 0;   // batches run_batch_api re-ran over the all-reduce path
   uint64_t loop_give_ups_ = 0;  // batches whose persistent loop gave up (forced ones included)
@@ -657,6 +661,7 @@ class Engine {
   DevBuf d_meta;                         // owns the three views below (ensure_scratch)
   DevBuf d_off, d_stats, d_results;      // views: program offsets + sizes, PodStats, DevResult
   DevBuf d_diag;                         // diagnosed calls: one kDiagWords row per pod (k_diag_reduce)
+  DevBuf d_diag_sum;                     // node-sharded: the rows summed over the ranks (Comm::all_reduce_sum_i32)
   int32_t* h_diag = nullptr;             // their pinned landing area
   size_t h_diag_rows = 0;
   DevBuf d_arena;  // PTS/IPA histograms; kept all-zero between pods (k_select re-zeroes what it used)

@@ -926,6 +926,12 @@ bool decode_config(const char* p, size_t n, Config* c, std::string* err) {
         *err = "distributed: exactly one of ncclId (RCCL) or localGroup (in-process ranks) is required";
         return false;
       }
+      if (const JVal* dg = d.get(*ds, "diagnosis")) c->shard_diagnosis = dg->type == JVal::BOOL && dg->b;
+      if (c->shard_diagnosis && !c->sharded()) {
+        *err = "distributed.diagnosis: true needs a node-sharded context (ncclId or localGroup); an unsharded "
+               "context diagnoses without it";
+        return false;
+      }
     }
     bool ok = true;
     d.each(d.get(r, "scoreWeights"), [&](const JVal& v) {
