@@ -136,7 +136,7 @@ typedef struct ksg_eval_out {
  *    "nodeAffinity": {"addedAffinity": <v1.NodeAffinity>},
  *    "podTopologySpread": {"defaultingType": "System" | "List",     (PodTopologySpreadArgs)
  *                          "defaultConstraints": [<v1.TopologySpreadConstraint without labelSelector>]},
- *    "nominatedPods": "Refuse" | "Evaluate",               (other pods' nominations, see ksg_add_nominated_pod)
+ *    "nominatedPods": "Refuse" | "Evaluate" | "EvaluateAll",   (other pods' nominations, see ksg_add_nominated_pod)
  *    "device": 0, "distributed": {"worldSize": 1, "rank": 0, "ncclId": "<hex>"}}
  * Absent keys take the upstream defaults.  Returns NULL on failure (ksg_create_error()). */
 ksg_ctx *ksg_create(const char *config_json, size_t len);
@@ -254,7 +254,16 @@ int ksg_forget(ksg_ctx *ctx, int32_t handle);
  *                       affinity or anti-affinity term, or (c) would see a nominated pod that has a required
  *                       anti-affinity term.  A batch is judged against the nominator as the call found it; inside
  *                       it pod i sees the nominator as pods 0..i-1 left it.
- * Any other value fails ksg_create (an invalid argument), and so does "Evaluate" on a node-sharded context. */
+ *   "EvaluateAll"       "Evaluate", and ksg_schedule_one / ksg_schedule_batch, their _diag forms and evaluation
+ *                       output also take the pairs (a)-(c): such a node is filtered twice as the reference does --
+ *                       with the pods nominated to it added, PodTopologySpread's and InterPodAffinity's AddPod
+ *                       applied at that node's own topology values only (a plugin whose PreFilter, which runs
+ *                       without them, returned Skip runs in neither pass), and, if that passes, as the node is;
+ *                       the first failing status is the node's.  The nominator then also keeps each nominated
+ *                       pod's namespace, labels and required anti-affinity terms.  Such pods take the per-pod
+ *                       launches rather than a persistent loop.  ksg_preempt is still refused for (a)-(c).
+ * Any other value fails ksg_create (an invalid argument), and so do "Evaluate" and "EvaluateAll" on a node-sharded
+ * context. */
 int ksg_add_nominated_pod(ksg_ctx *ctx, const char *pod_json, size_t len);
 int ksg_delete_nominated_pod(ksg_ctx *ctx, const char *uid);
 

@@ -183,6 +183,9 @@ enum DescFlags : uint32_t {
                                    // 657-669,714-745); feasible: the pod goes there, else the full pass follows
   DF_DIAG = 1u << 25,              // a diagnosed call (ksg_schedule_*_diag): the node pass stores the status word as
                                    // DF_EVAL_OUT does (not the score vectors) and k_diag_reduce follows k_select
+  DF_NOM_TOPO = 1u << 26,          // config nominatedPods "EvaluateAll": a nominee the pod would see may move a count
+                                   // its PodTopologySpread / InterPodAffinity Filter reads -- k_nom_topo runs behind
+                                   // k_aggregate and the node pass is the two-pass instance (launch path only)
 };
 // a pod the per-pod path may place before its full evaluation (PodStats::ob_done: 1 hint, 2 nominated node)
 constexpr uint32_t DF_EARLY = DF_OB | DF_NOMINATED;
@@ -258,7 +261,9 @@ struct PodDesc {
   // ---- other pods' nominations (config nominatedPods "Evaluate", MirrorView::nom)
   int32_t nom_self;                    // this pod's own record in the nominee table (never in its G), -1: none
   int32_t nom_prio;                    // corev1helpers.PodPriority: G(p, n) is node n's records of priority >= this
-  int32_t nom_pad;                     // (both 0 / -1 while no nominee table is staged: programs compare as before)
+  int32_t nom_rows;                    // DF_NOM_TOPO: the arena word where the pod's nominee delta rows start (past
+                                       // its histograms, inside arena_words, so k_select zeroes them again); else 0
+                                       // (all three 0 / -1 while no nominee table is staged: programs compare as before)
 };
 
 // ---- the nominee table (RunFilterPluginsWithNominatedPods) ------------------------------
@@ -269,6 +274,10 @@ struct PodDesc {
 struct NomHdr {
   int32_t n_rec;
   int32_t rec_off, port_off, sc_off;  // byte offsets of NomRec[], uint32_t port ids[], ScalarReq[]
+  // config nominatedPods "EvaluateAll" (else 0): what PodTopologySpread's and InterPodAffinity's AddPod read of a
+  // nominee -- NomTopoRec[n_rec] (parallel to the records), its labels (the pod table's lbl_pool encoding), its
+  // required anti-affinity terms (NomTerm[]) and their selector / namespace pool (int32, as MirrorView::term_pool)
+  int32_t topo_off, lbl_off, term_off, tpool_off;
 };
 struct NomRec {
   int64_t cpu, mem, eph;       // PodInfo.CalculateResource (Requested)
@@ -277,6 +286,26 @@ struct NomRec {
   int32_t sc_lo, sc_cnt;       // its scalar resources in the ScalarReq pool (mirror columns)
   int32_t pad;
 };
+struct NomTopoRec {
+  int32_t node;                // snapshot index of the nominated node
+  int32_t ns;                  // namespace id
+  int32_t lbl_lo, lbl_cnt;     // its sorted label set in the label pool
+  int32_t term_lo, term_cnt;   // its required anti-affinity terms
+  int32_t pad[2];
+};
+struct NomTerm {
+  DTerm t;                     // as the existing-term table holds it (owner: the record; offsets into the table's pool)
+  int32_t slot;                // label column of the term's topology key
+  int32_t pad;
+};
+// A marked pod's delta rows (PodDesc::nom_rows): one row of n_ptsf + 2 + n_ranti arena words per nominee record
+// index, node i's row being the one of its first record (head[i]); k_nom_topo adds to them:
+//   [c < n_ptsf]     nominees of G(p, i) PodTopologySpread's AddPod counts for DoNotSchedule constraint c
+//   [n_ptsf]         nominees matching all of the pod's required affinity terms
+//   [n_ptsf + 1]     nominees one of whose required anti-affinity terms matches the pod, node i carrying its key
+//   [n_ptsf + 2 + k] nominees matching the pod's required anti-affinity term k
+// and behind the rows, k_pts_minima's (minimum, multiplicity, next count) per DoNotSchedule constraint.
+KSG_HD inline int32_t nom_row_words(int32_t n_ptsf, int32_t n_ranti) { return n_ptsf + 2 + n_ranti; }
 constexpr uint32_t NF_NOMINEES = 1u << 31;  // NodeCore::flags (not the mirror's column): the node has nominee records
 
 // ---- DefaultPreemption: SelectVictimsOnNode per node, one thread each ----------

@@ -344,13 +344,20 @@ __device__ __forceinline__ uint32_t topo_filters(const MirrorView& m, const uint
 template <typename Topo>
 __device__ uint32_t run_filters_node(const MirrorView& m, const NodeCore& nc, const uint8_t* base, const PodDesc& d, int i,
                                      int64_t* raw_taint, const Topo& tp, int ls);
-// ... with the pods nominated to node i added (nom_status)
-template <bool NOM = true, typename Topo>
+template <typename Topo>
+__device__ __forceinline__ uint32_t nom_status_topo(const MirrorView& m, const NodeCore& nc, const uint8_t* base,
+                                                    const PodDesc& d, int i, uint32_t st0, const Topo& tp);
+// ... with the pods nominated to node i added (nom_status; NT: a marked pod's two passes, nom_status_topo -- the
+// launch path's k_filter_score_nt / k_nominated_nt / k_ob_hint_nt only, Topo = ArenaTopo)
+template <bool NOM = true, bool NT = false, typename Topo>
 __device__ uint32_t run_filters(const MirrorView& m, const NodeCore& nc, const uint8_t* base, const PodDesc& d, int i,
                                 int64_t* raw_taint, const Topo& tp, int ls) {
   uint32_t st = run_filters_node(m, nc, base, d, i, raw_taint, tp, ls);
-  if constexpr (NOM)
+  if constexpr (NT) {
+    if (m.nom != nullptr && (nc.flags & NF_NOMINEES)) st = nom_status_topo(m, nc, base, d, i, st, tp);
+  } else if constexpr (NOM) {
     if (m.nom != nullptr && (nc.flags & NF_NOMINEES)) st = nom_status(m, nc, base, d, i, st);
+  }
   return st;
 }
 template <typename Topo>
@@ -477,6 +484,83 @@ __device__ __forceinline__ uint32_t topo_filters(const MirrorView& m, const uint
   return 0;
 }
 
+// ---- nominees that move spread / affinity counts (config nominatedPods "EvaluateAll") -----------
+// Pass 1 of RunFilterPluginsWithNominatedPods for node i of a marked pod: the cloned PreFilter state after the
+// AddPod of every pod in G(p, i), at node i's own topology values only -- the pod's counts (ArenaTopo) plus node i's
+// delta row (k_nom_topo; desc.h nom_row_words).  A count is asked for by its histogram base: constraint c's own
+// histogram gets row[c]; the required affinity terms' histograms get the "matches all terms" count (AddPod adds at
+// every term's key); a required anti-affinity term's gets the counts of every term sharing its histogram (one per
+// topology key).  The constraint minimum follows criticalPaths.update for a pure addition: min(own count + delta,
+// minimum over the other domains), the latter k_pts_minima's next count if node i's domain held the minimum alone.
+struct NomTopo {
+  ArenaTopo a;
+  const MirrorView& m;
+  const uint8_t* base;
+  const PodDesc& d;
+  int i;
+  const unsigned long long* row;  // node i's delta row
+  const long long* mm;            // k_pts_minima: (minimum, multiplicity, next) per DoNotSchedule constraint
+  __device__ __forceinline__ int64_t cnt(int32_t hist_base, int32_t lref, int32_t v, int ls) const {
+    int64_t x = a.cnt(hist_base, lref, v, ls);
+    const PtsCons* cs = at<PtsCons>(base, d.ptsf_off);
+    for (int32_t c = 0; c < d.n_ptsf; ++c)
+      if (cs[c].hist_base == hist_base) x += (int64_t)row[c];
+    const IpaTerm* ra = at<IpaTerm>(base, d.raff_off);
+    bool aff = false;
+    for (int32_t k = 0; k < d.n_raff; ++k) aff |= ra[k].hist_base == hist_base;
+    if (aff) x += (int64_t)row[d.n_ptsf];
+    const IpaTerm* rn = at<IpaTerm>(base, d.ranti_off);
+    for (int32_t k = 0; k < d.n_ranti; ++k)
+      if (rn[k].hist_base == hist_base) x += (int64_t)row[d.n_ptsf + 2 + k];
+    return x;
+  }
+  __device__ __forceinline__ int64_t pmin(int c) const {
+    const int64_t dl = (int64_t)row[c];
+    const PtsCons& cs = at<PtsCons>(base, d.ptsf_off)[c];
+    const int32_t v = node_label(m, cs.slot, i);
+    if (dl == 0 || v < 0) return a.pmin(c);
+    const int64_t own = (int64_t)a.arena[cs.hist_base + v];
+    const int64_t others = (own == mm[3 * c] && mm[3 * c + 1] == 1) ? mm[3 * c + 2] : mm[3 * c];
+    return own + dl < others ? own + dl : others;
+  }
+  __device__ __forceinline__ uint32_t pndom(int c) const { return a.pndom(c); }
+  __device__ __forceinline__ uint32_t any() const {
+    uint32_t x = a.any();
+    if (row[d.n_ptsf]) x |= 1u;  // affinityCounts is no longer empty
+    for (int32_t k = 0; k < d.n_ranti; ++k)
+      if (row[d.n_ptsf + 2 + k]) x |= 2u;
+    return x;
+  }
+};
+// The node's status for a marked pod (framework.go:1211-1294): pass 1 with G(p, i) added -- a failure of a plugin
+// before NodePorts stands in both passes; NodePorts and NodeResourcesFit on core + G (nom_status); PodTopologySpread
+// and InterPodAffinity on the counts with G's AddPod (NomTopo), InterPodAffinity only if its PreFilter, which ran
+// without nominees, did not Skip (no required term of the pod's, no existing term matching it: a nominee's
+// anti-affinity term against the pod is then never checked).  Pass 1's failure is the node's status; else pass 2's,
+// st0 -- no monotonicity: an affinity only a nominee satisfies passes pass 1 and fails pass 2.
+template <typename Topo>
+__device__ __forceinline__ uint32_t nom_status_topo(const MirrorView& m, const NodeCore& nc, const uint8_t* base,
+                                                    const PodDesc& d, int i, uint32_t st0, const Topo& tp) {
+  if (!(d.flags & DF_NOM_TOPO)) return nom_status(m, nc, base, d, i, st0);
+  const uint32_t p0 = status_plugin(st0);
+  if (st0 != 0 && (p0 < (uint32_t)P_FIT || p0 > (uint32_t)P_IPA)) return st0;
+  const NomG g = nom_gather(m, base, d, i);
+  if (g.pods == 0) return st0;
+  uint32_t st1 = nom_status(m, nc, base, d, i, 0u);
+  if (st1 == 0) {
+    const int32_t w = nom_row_words(d.n_ptsf, d.n_ranti);
+    const NomHdr& h = *reinterpret_cast<const NomHdr*>(m.nom);
+    const unsigned long long* rows = tp.arena + d.nom_rows;
+    const unsigned long long* row = rows + (size_t)nom_head(m.nom)[i] * (size_t)w;
+    const NomTopo nt{ArenaTopo{tp.ps, tp.arena}, m, base, d, i, row,
+                     reinterpret_cast<const long long*>(rows + (size_t)h.n_rec * (size_t)w)};
+    st1 = topo_filters(m, base, d, i, nt, 0);
+    const bool ipa = ((d.filter_mask >> P_IPA) & 1u) && (d.n_raff > 0 || d.n_ranti > 0 || (tp.any() & 4u));
+    if (st1 == 0 && ipa && row[d.n_ptsf + 1]) st1 = pack_status(C_UNSCHED, P_IPA, KSG_R_IPA_EXISTING_ANTI);
+  }
+  return st1 ? st1 : st0;
+}
+
 // ---- wave/block reductions ------------------------------------------------------------------------
 // DPP scan steps (row_shr 1/2/4/8, row_bcast 15/31; disabled or out-of-row lanes contribute 0, the
 // identity of an unsigned max or sum): the wave's result ends in lane 63.  All 64 lanes active.
@@ -533,7 +617,7 @@ struct NodeEval {
 // 1378-1402).  kStore: write the node's status word (evaluation output), the weighted sum of the
 // non-normalising scores and the raw scores the normalising plugins need to the batch scratch
 // (the launch path's k_select reads them back; the persistent loop keeps them in registers).
-template <bool kStore, bool NOM = true>
+template <bool kStore, bool NOM = true, bool NT = false>
 __device__ __forceinline__ NodeEval eval_node(const MirrorView& m, const BatchView& b, const uint8_t* base, const PodDesc& d, int pod,
                               int i, bool valid) {
   const bool eval = (d.flags & DF_EVAL_OUT) != 0;
@@ -559,7 +643,7 @@ __device__ __forceinline__ NodeEval eval_node(const MirrorView& m, const BatchVi
       st = in ? 0u : pack_status(C_UU, 15u, KSG_R_PREFILTER);
     }
     if (st == 0) {
-      uint32_t f = run_filters<NOM>(m, nc, base, d, i, &raw_taint, ArenaTopo{b.stats + pod, b.arena}, 0);
+      uint32_t f = run_filters<NOM, NT>(m, nc, base, d, i, &raw_taint, ArenaTopo{b.stats + pod, b.arena}, 0);
       if (d.flags & DF_ALL_FEASIBLE)  // plugin-eval mode: the caller's node list is the feasible list
         f = ((d.flags & DF_NODE_LIST) && !bit(base, d.node_list_off, (uint32_t)i, (m.n + 31) / 32))
                 ? pack_status(C_UU, 15u, 0u)
@@ -836,8 +920,9 @@ __device__ __forceinline__ bool ob_skip(const BatchView& b, int pod) {
 // =====================================================================================================
 // k_filter_score
 // =====================================================================================================
-template <bool kLds>
-__global__ __launch_bounds__(kBlock) void k_filter_score(MirrorView m, BatchView b, int pod, int blk0) {
+// NT: the instance a marked pod runs (config nominatedPods "EvaluateAll": both passes on nodes with nominees)
+template <bool kLds, bool NT>
+__device__ __forceinline__ void filter_score(const MirrorView& m, const BatchView& b, int pod, int blk0) {
   __shared__ __align__(16) uint8_t s_blob[kLds ? kBlobLds : 16];
   if (ob_skip(b, pod)) return;
   const uint8_t* base = b.descs + b.desc_off[pod];
@@ -850,7 +935,7 @@ __global__ __launch_bounds__(kBlock) void k_filter_score(MirrorView m, BatchView
   const int blk = blk0 + (int)blockIdx.x;  // node-sharded launches cover blocks [blk0, blk0 + gridDim.x)
   const int i = blk * kBlock + threadIdx.x;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const NodeEval ne = eval_node<true>(m, b, base, d, pod, i, i < m.n);
+  const NodeEval ne = eval_node<true, true, NT>(m, b, base, d, pod, i, i < m.n);
   const bool feas = ne.st == 0;
   const unsigned long long ballot = __ballot(feas);
   if (lane == 0) b.fmask[(size_t)blk * (kBlock / 64) + wave] = ballot;
@@ -902,6 +987,14 @@ __global__ __launch_bounds__(kBlock) void k_filter_score(MirrorView m, BatchView
       if (pc) atomicAdd(&ps->pts_nonignored, pc);
     }
   }
+}
+template <bool kLds>
+__global__ __launch_bounds__(kBlock) void k_filter_score(MirrorView m, BatchView b, int pod, int blk0) {
+  filter_score<kLds, false>(m, b, pod, blk0);
+}
+template <bool kLds>
+__global__ __launch_bounds__(kBlock) void k_filter_score_nt(MirrorView m, BatchView b, int pod, int blk0) {
+  filter_score<kLds, true>(m, b, pod, blk0);
 }
 
 // =====================================================================================================
@@ -1269,7 +1362,8 @@ constexpr int64_t kObMaxAgeNs = 500LL * 1000 * 1000;  // maxBatchAge (batch.go:5
 // then evaluateNominatedNode with the hint (schedule_one.go:718-752): the hinted node's filters alone.
 // Feasible: the pod is placed there (schedulePod's one-feasible-node path, :586-598) and
 // StoreScheduleResults(hinted == chosen) keeps the rest of the heap (:110-118).
-__global__ void k_ob_hint(MirrorView m, BatchView b, int pod) {
+template <bool NT>
+__device__ __forceinline__ void ob_hint(const MirrorView& m, const BatchView& b, int pod) {
   if (threadIdx.x != 0) return;
   const uint8_t* base = b.descs + b.desc_off[pod];
   const PodDesc& d = *reinterpret_cast<const PodDesc*>(base);
@@ -1279,7 +1373,7 @@ __global__ void k_ob_hint(MirrorView m, BatchView b, int pod) {
   if (st.len <= 0 || st.last_cycle != d.ob_cycle - 1 || d.ob_now > st.creation + kObMaxAgeNs || st.last_node < 0) return;
   int64_t rt = 0;
   const ArenaTopo at{ps, b.arena};
-  if (run_filters(m, load_core(m, st.last_node), base, d, st.last_node, &rt, at, 0) == 0) return;  // not full
+  if (run_filters<true, NT>(m, load_core(m, st.last_node), base, d, st.last_node, &rt, at, 0) == 0) return;  // not full
   ObEnt* h = b.ob_heap;
   const int n = st.len - 1;  // heap.Pop: swap(0, n), down(0, n), take the last
   const ObEnt top = h[0];
@@ -1289,7 +1383,7 @@ __global__ void k_ob_hint(MirrorView m, BatchView b, int pod) {
   st.len = n;
   const int hint = top.node;
   if (hint < 0 || hint >= m.n) return;  // no longer in the snapshot: an error, then the full pass
-  if (run_filters(m, load_core(m, hint), base, d, hint, &rt, at, 0) != 0) {  // the full pass decides
+  if (run_filters<true, NT>(m, load_core(m, hint), base, d, hint, &rt, at, 0) != 0) {  // the full pass decides
     ps->nom_failed = (uint32_t)hint + 1u;  // its status is in NodeToStatus (k_sample_find counts it once)
     return;
   }
@@ -1304,13 +1398,16 @@ __global__ void k_ob_hint(MirrorView m, BatchView b, int pod) {
   st.last_cycle = d.ob_cycle;
   st.last_node = hint;
 }
+__global__ void k_ob_hint(MirrorView m, BatchView b, int pod) { ob_hint<false>(m, b, pod); }
+__global__ void k_ob_hint_nt(MirrorView m, BatchView b, int pod) { ob_hint<true>(m, b, pod); }
 
 // k_nominated (one thread, after PreFilter and the pod's histograms): evaluateNominatedNode (schedule_one.go:657-669,
 // 714-745) for status.nominatedNodeName -- that node's filters alone (RunFilterPluginsWithNominatedPods: with the
 // other pods nominated to it added, run_filters; the pod's own record is never in its G).  Feasible: the pod is placed there (schedulePod's one-feasible-node
 // path, :586-598; nextStartNodeIndex stays).  Else the node's status joins NodeToStatus (kept for evaluation
 // output, counted once by k_sample_find) and the full pass follows.
-__global__ void k_nominated(MirrorView m, BatchView b, int pod) {
+template <bool NT>
+__device__ __forceinline__ void nominated(const MirrorView& m, const BatchView& b, int pod) {
   if (threadIdx.x != 0) return;
   const uint8_t* base = b.descs + b.desc_off[pod];
   const PodDesc& d = *reinterpret_cast<const PodDesc*>(base);
@@ -1319,7 +1416,7 @@ __global__ void k_nominated(MirrorView m, BatchView b, int pod) {
   const int nn = d.nominated_node;
   if (nn < 0 || nn >= m.n) return;
   int64_t rt = 0;
-  const uint32_t st = run_filters(m, load_core(m, nn), base, d, nn, &rt, ArenaTopo{ps, b.arena}, 0);
+  const uint32_t st = run_filters<true, NT>(m, load_core(m, nn), base, d, nn, &rt, ArenaTopo{ps, b.arena}, 0);
   if (st != 0) {
     ps->nom_failed = (uint32_t)nn + 1u;
     if (d.flags & (DF_EVAL_OUT | DF_DIAG)) b.status[nn] = st;
@@ -1334,6 +1431,8 @@ __global__ void k_nominated(MirrorView m, BatchView b, int pod) {
   b.results[pod].evaluated = 1;  // EvaluatedNodes = 1 + diagnosis.NodeToStatus.Len() (no failure yet)
   ps->ob_done = 2u;
 }
+__global__ void k_nominated(MirrorView m, BatchView b, int pod) { nominated<false>(m, b, pod); }
+__global__ void k_nominated_nt(MirrorView m, BatchView b, int pod) { nominated<true>(m, b, pod); }
 
 // ---- FitError diagnosis ------------------------------------------------------------------------
 // diag_accumulate: every wave that holds nodes of the pod brings one packed Filter status per lane (valid: the lane
@@ -5143,6 +5242,72 @@ __global__ __launch_bounds__(kAggThreads) void k_agg_loop_group_diag(const AggGr
   agg_loop_body<true, PTSS, false, kMaxSweep, true, true>(a.m, a.b, a.av, (int)blockIdx.x - r * G);
 }
 
+// k_nom_topo (a marked pod, behind k_aggregate; config nominatedPods "EvaluateAll"): what PodTopologySpread's and
+// InterPodAffinity's AddPod (podtopologyspread/filtering.go:170-213, interpodaffinity/filtering.go:102-122) would
+// add to the pod's PreFilter state for each nominee, kept per nominated node instead of in the shared counts: the
+// reference adds node n's nominees for node n's pass 1 only.  One thread per nominee record; a record outside
+// G(p, n) -- priority below the pod's, or the pod's own -- adds nothing.  The thread matches its nominee against the
+// pod's programs as k_aggregate's pod and term roles match a bound pod, and adds to its node's row (desc.h
+// nom_row_words) with relaxed agent-scope atomics.  The rows are zero on entry (the arena is all-zero between
+// pods) and are read by the next kernels on the stream only.
+__global__ __launch_bounds__(kBlock) void k_nom_topo(MirrorView m, BatchView b, int pod) {
+  const uint8_t* base = b.descs + b.desc_off[pod];
+  const PodDesc& d = *reinterpret_cast<const PodDesc*>(base);
+  if (!(d.flags & DF_NOM_TOPO) || m.nom == nullptr) return;
+  const uint8_t* tab = m.nom;
+  const NomHdr& h = *reinterpret_cast<const NomHdr*>(tab);
+  const int q = blockIdx.x * kBlock + threadIdx.x;
+  if (q >= h.n_rec || h.topo_off == 0) return;
+  const NomRec* rec = reinterpret_cast<const NomRec*>(tab + h.rec_off);
+  if (rec[q].prio < d.nom_prio || q == d.nom_self) return;
+  const NomTopoRec t = reinterpret_cast<const NomTopoRec*>(tab + h.topo_off)[q];
+  const int n = t.node;
+  if (n < 0 || n >= m.n) return;
+  const unsigned long long* pl = reinterpret_cast<const unsigned long long*>(tab + h.lbl_off) + t.lbl_lo;
+  const int32_t pn = t.lbl_cnt, pns = t.ns;
+  const int32_t* sp = at<int32_t>(base, d.sel_pool_off);
+  unsigned long long* row = b.arena + d.nom_rows + (size_t)nom_head(tab)[n] * (size_t)nom_row_words(d.n_ptsf, d.n_ranti);
+  auto add = [&](int32_t w) {
+    (void)__hip_atomic_fetch_add(row + w, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  };
+  const uint32_t fm = d.filter_mask;
+  if (((fm >> P_PTS) & 1u) && d.n_ptsf && pns == d.ns_id) {  // updateWithPod (filtering.go:185-213)
+    const PtsCons* cs = at<PtsCons>(base, d.ptsf_off);
+    const uint32_t el = pts_eligible(m, base, d, cs, d.n_ptsf, n);
+    for (int32_t c = 0; c < d.n_ptsf; ++c)
+      if (((el >> c) & 1u) && !lsel_empty(sp + cs[c].sel) && lsel_match(sp + cs[c].sel, pl, pn)) add(c);
+  }
+  if (!((fm >> P_IPA) & 1u)) return;
+  if (d.n_raff) {  // affinityCounts.updateWithAffinityTerms: the nominee matches all required affinity terms
+    const IpaTerm* ts = at<IpaTerm>(base, d.raff_off);
+    bool all = true, key = false;
+    for (int32_t k = 0; k < d.n_raff; ++k) {
+      all = all && term_matches_pod(sp, ts[k], pns, pl, pn);
+      key = key || node_label(m, ts[k].slot, n) >= 0;
+    }
+    if (all && key) add(d.n_ptsf);
+  }
+  if (d.n_ranti) {  // antiAffinityCounts.updateWithAntiAffinityTerms
+    const IpaTerm* ts = at<IpaTerm>(base, d.ranti_off);
+    for (int32_t k = 0; k < d.n_ranti; ++k)
+      if (term_matches_pod(sp, ts[k], pns, pl, pn) && node_label(m, ts[k].slot, n) >= 0) add(d.n_ptsf + 2 + k);
+  }
+  // existingAntiAffinityCounts: the nominee's required anti-affinity terms against the pod (AffinityTerm.Matches
+  // with the pod's namespace labels, as k_aggregate's term role)
+  const NomTerm* nts = reinterpret_cast<const NomTerm*>(tab + h.term_off);
+  const int32_t* tp = reinterpret_cast<const int32_t*>(tab + h.tpool_off);
+  const unsigned long long* il = at<unsigned long long>(base, d.lbl_off);
+  const unsigned long long* nl = at<unsigned long long>(base, d.nslbl_off);
+  bool ex = false;
+  for (int32_t k = 0; k < t.term_cnt && !ex; ++k) {
+    const NomTerm& nt = nts[t.term_lo + k];
+    if (nt.slot < 0 || node_label(m, nt.slot, n) < 0) continue;
+    ex = (id_in(tp + nt.t.ns_off, nt.t.ns_cnt, d.ns_id) || lsel_match(tp + nt.t.nssel, nl, d.n_nslbl)) &&
+         lsel_match(tp + nt.t.sel, il, d.n_lbl);
+  }
+  if (ex) add(d.n_ptsf + 1);
+}
+
 }  // namespace ksg
 
 // ---- host-side launchers (C++ linkage, called by the host library) ------------------------------
@@ -5165,6 +5330,32 @@ hipError_t launch_filter_score(const MirrorView& m, const BatchView& b, int pod,
     else
       hipLaunchKernelGGL(k_filter_score<false>, dim3(nblk), dim3(kBlock), 0, s, m, b, pod, blk0);
   }
+  return hipGetLastError();
+}
+// the two-pass instances a marked pod runs (DF_NOM_TOPO; every node block)
+hipError_t launch_filter_score_nt(const MirrorView& m, const BatchView& b, int pod, hipStream_t s, hipEvent_t t0,
+                                  hipEvent_t t1, bool lds) {
+  const int nblk = (m.n + kBlock - 1) / kBlock;
+  if (nblk == 0) return hipSuccess;
+  if (lds) {
+    if (t0)
+      hipExtLaunchKernelGGL(k_filter_score_nt<true>, dim3(nblk), dim3(kBlock), 0, s, t0, t1, 0, m, b, pod, 0);
+    else
+      hipLaunchKernelGGL(k_filter_score_nt<true>, dim3(nblk), dim3(kBlock), 0, s, m, b, pod, 0);
+  } else {
+    if (t0)
+      hipExtLaunchKernelGGL(k_filter_score_nt<false>, dim3(nblk), dim3(kBlock), 0, s, t0, t1, 0, m, b, pod, 0);
+    else
+      hipLaunchKernelGGL(k_filter_score_nt<false>, dim3(nblk), dim3(kBlock), 0, s, m, b, pod, 0);
+  }
+  return hipGetLastError();
+}
+hipError_t launch_ob_hint_nt(const MirrorView& m, const BatchView& b, int pod, hipStream_t s) {
+  hipLaunchKernelGGL(k_ob_hint_nt, dim3(1), dim3(64), 0, s, m, b, pod);
+  return hipGetLastError();
+}
+hipError_t launch_nominated_nt(const MirrorView& m, const BatchView& b, int pod, hipStream_t s) {
+  hipLaunchKernelGGL(k_nominated_nt, dim3(1), dim3(64), 0, s, m, b, pod);
   return hipGetLastError();
 }
 hipError_t launch_select(const MirrorView& m, const BatchView& b, int pod, hipStream_t s, bool lds) {
@@ -5571,7 +5762,12 @@ hipError_t warm_kernels() {
                       reinterpret_cast<const void*>(&k_sched_loop_group_diag<4>),
                       reinterpret_cast<const void*>(&k_agg_loop<true, true, false, kMaxSweep, true>),
                       reinterpret_cast<const void*>(&k_agg_loop_group_diag<true>),
-                      reinterpret_cast<const void*>(&k_sum_reduce)};
+                      reinterpret_cast<const void*>(&k_sum_reduce),
+                      reinterpret_cast<const void*>(&k_filter_score_nt<true>),
+                      reinterpret_cast<const void*>(&k_filter_score_nt<false>),
+                      reinterpret_cast<const void*>(&k_ob_hint_nt),
+                      reinterpret_cast<const void*>(&k_nominated_nt),
+                      reinterpret_cast<const void*>(&k_nom_topo)};
   for (const void* f : fs) {
     const hipError_t e = hipFuncGetAttributes(&a, f);
     if (e != hipSuccess) return e;
@@ -5833,6 +6029,16 @@ hipError_t launch_pts_minima(const BatchView& b, int pod, int ncons, long long* 
   if (ncons <= 0) return hipSuccess;
   hipLaunchKernelGGL(k_pts_minima, dim3(ncons), dim3(kBlock), 0, s, b, pod, mm);
   return hipGetLastError();
+}
+// A marked pod's nominee deltas and, behind its rows in the arena, k_pts_minima's triples (both between k_aggregate,
+// which fills the counts, and k_select, which zeroes the pod's arena words again).
+hipError_t launch_nom_topo(const MirrorView& m, const BatchView& b, int pod, const PodDesc& d, int nrec, hipStream_t s) {
+  if (nrec <= 0) return hipSuccess;
+  hipLaunchKernelGGL(k_nom_topo, dim3((nrec + kBlock - 1) / kBlock), dim3(kBlock), 0, s, m, b, pod);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  long long* mm = reinterpret_cast<long long*>(b.arena + d.nom_rows + (size_t)nrec * (size_t)nom_row_words(d.n_ptsf, d.n_ranti));
+  return launch_pts_minima(b, pod, d.n_ptsf, mm, s);
 }
 
 // The existing pods' required anti-affinity terms that match the preemptor (the term role of k_aggregate,

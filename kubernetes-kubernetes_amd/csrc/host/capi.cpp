@@ -83,7 +83,8 @@ ksg_ctx* ksg_create(const char* config_json, size_t len) {
     }
     if (cfg.sharded()) {  // node-sharded: join the exchange group (collective across the ranks)
       if (cfg.nominated_evaluate) {  // (every rank has the same config, so all fail here)
-        g_create_error = "nominatedPods \"Evaluate\" on a node-sharded context: the sharded loops do not filter with "
+        g_create_error = std::string("nominatedPods \"") + (cfg.nominated_all ? "EvaluateAll" : "Evaluate") +
+                         "\" on a node-sharded context: the sharded loops do not filter with "
                          "nominated pods; use \"Refuse\" (the default)";
         delete ctx;
         return nullptr;
@@ -436,8 +437,9 @@ int ksg_preempt(ksg_ctx* ctx, int32_t handle, const char* args_json, size_t args
     if (it == ctx->engine->queue.end()) return KSG_ENOTFOUND;
     // node-sharded contexts: every rank holds the whole mirror and pod table, so each rank runs the
     // PostFilter over every node by itself (no exchange) and returns the identical choice
-    // (SelectVictimsOnNode filters with the nominated pods too: refused likewise)
-    if (const int rn = ctx->engine->check_nominations({&it->second})) return with_err(ctx, rn);
+    // (SelectVictimsOnNode filters with the nominated pods too: refused likewise -- under "EvaluateAll" as well,
+    // where every reprieve step would need both passes)
+    if (const int rn = ctx->engine->check_nominations({&it->second}, true)) return with_err(ctx, rn);
     if (const int rs = quiesce(ctx)) return rs;
     std::string d;
     const int rc = ctx->engine->preempt(it->second, args_json, args_len, result, detail ? &d : nullptr);

@@ -80,6 +80,13 @@ hipError_t warm_aggregate();
 hipError_t launch_ob_hint(const MirrorView& m, const BatchView& b, int pod, hipStream_t s);
 hipError_t launch_nominated(const MirrorView& m, const BatchView& b, int pod, hipStream_t s);
 hipError_t launch_ob_store(const BatchView& b, int pod, hipStream_t s);
+// config nominatedPods "EvaluateAll", a marked pod (DF_NOM_TOPO): k_nom_topo (+ k_pts_minima) behind k_aggregate, and
+// the two-pass instances of the node pass, k_nominated and k_ob_hint
+hipError_t launch_nom_topo(const MirrorView& m, const BatchView& b, int pod, const PodDesc& d, int nrec, hipStream_t s);
+hipError_t launch_filter_score_nt(const MirrorView& m, const BatchView& b, int pod, hipStream_t s, hipEvent_t t0,
+                                  hipEvent_t t1, bool lds);
+hipError_t launch_ob_hint_nt(const MirrorView& m, const BatchView& b, int pod, hipStream_t s);
+hipError_t launch_nominated_nt(const MirrorView& m, const BatchView& b, int pod, hipStream_t s);
 hipError_t launch_diag_reduce(const MirrorView& m, const BatchView& b, int pod, int32_t* rows, hipStream_t s, int blk0 = 0,
                               int nblk = -1);
 hipError_t launch_ob_remap(ObState* st, ObEnt* h, const int32_t* map, int nold, int maxlen, hipStream_t s);
@@ -534,6 +541,14 @@ int Engine::compile(const PodSpec& p, Mode mode, int plugin, bool assume, bool e
   {
     const int rc = compile_topology(p, mode, plugin, N, &B, &D, &fmask, &smask, out);
     if (rc) return rc;
+  }
+  // "EvaluateAll": a pod check_nominations marked gets its delta rows and k_pts_minima's triples behind its
+  // histograms (desc.h nom_row_words); the arena stays all-zero between pods, k_select clears the rows with the rest
+  if (mode == CYCLE && nom_active_ && nom_marked_.count(&p)) {
+    D.flags |= DF_NOM_TOPO;
+    D.nom_rows = D.arena_words;
+    D.arena_words += nom_nrec_ * nom_row_words(D.n_ptsf, D.n_ranti) + 3 * D.n_ptsf;
+    out->arena_words = D.arena_words;
   }
   mark(3);
 
@@ -1165,7 +1180,7 @@ int Engine::ob_sync(hipStream_t s) {
 bool Engine::loop_ok(const CompiledPod& p) const {
   if (p.error) return false;
   const PodDesc& d = *reinterpret_cast<const PodDesc*>(p.blob.data());
-  if (d.flags & (DF_AGGREGATE | DF_EVAL_OUT | DF_SCORE_ERROR | DF_ALL_FEASIBLE | DF_EARLY)) return false;
+  if (d.flags & (DF_AGGREGATE | DF_EVAL_OUT | DF_SCORE_ERROR | DF_ALL_FEASIBLE | DF_EARLY | DF_NOM_TOPO)) return false;
   if (d.score_mask & ((1u << P_PTS) | (1u << P_IPA))) return false;
   // percentageOfNodesToScore / no-score profiles: the loop cuts the list and carries nextStartNodeIndex
   // itself (k_sched_loop), unsharded, over the whole snapshot (no PreFilterResult)
@@ -1177,7 +1192,8 @@ bool Engine::loop_ok(const CompiledPod& p) const {
 bool Engine::agg_loop_ok(const CompiledPod& p) const {
   if (p.error || !p.agg_ok || p.blob.size() > (size_t)kAggBlobLds) return false;
   const PodDesc& d = *reinterpret_cast<const PodDesc*>(p.blob.data());
-  if (d.flags & (DF_EVAL_OUT | DF_SCORE_ERROR | DF_ALL_FEASIBLE | DF_ROTDEV | DF_PREFILTER_REJECT | DF_SUBSET | DF_EARLY))
+  if (d.flags & (DF_EVAL_OUT | DF_SCORE_ERROR | DF_ALL_FEASIBLE | DF_ROTDEV | DF_PREFILTER_REJECT | DF_SUBSET | DF_EARLY |
+                 DF_NOM_TOPO))
     return false;
   // the fold plan holds <= 8 items per kind of the next pod's constraints / terms plus one per own
   // term of the pod just placed (kFoldMax = 80 in k_agg_loop)
@@ -1669,7 +1685,11 @@ int Engine::group_launch(GroupReq* req, bool agg, int nwg, int unit) {
 // constraint (its own or a profile default) or (b) a required pod affinity / anti-affinity term, or (c) a pod it
 // would see added has a required anti-affinity term (InterPodAffinity's existing-pod check).  A batch is judged
 // against the nominator as the call found it.
-int Engine::check_nominations(const std::vector<const PodSpec*>& pods) {
+// "EvaluateAll" schedules those pairs too: such a pod is marked (DF_NOM_TOPO at compile) and takes the launch path's
+// two-pass instances, k_nom_topo's deltas behind k_aggregate.  A mark is a superset -- a marked pod whose G is empty
+// by its turn finds no record and is evaluated as any other.  ksg_preempt (preempt) stays refused.
+int Engine::check_nominations(const std::vector<const PodSpec*>& pods, bool preempt) {
+  nom_marked_.clear();
   if (nominated.empty()) return KSG_OK;
   c->order();  // (the snapshot's index, current)
   const bool evaluate = nom_evaluate();
@@ -1704,6 +1724,10 @@ int Engine::check_nominations(const std::vector<const PodSpec*>& pods) {
       why = "(b) the pod has a required pod affinity or anti-affinity term, whose counts the nominated pod may move";
     else if (anti)
       why = "(c) the nominated pod has a required pod anti-affinity term, which InterPodAffinity would check against the pod";
+    if (why && c->cfg.nominated_all && !preempt) {
+      nom_marked_.insert(p);
+      continue;
+    }
     if (why) {
       c->err = who + "; " + why + " (RunFilterPluginsWithNominatedPods for such a pair runs outside the device path)";
       return KSG_ENOTSUP;
@@ -1736,6 +1760,11 @@ void Engine::nominate(const PodSpec& p) {
       if (k.sidecar) take(k);
     for (const Container& k : p.containers) take(k);
     nm.req_anti = !p.anti_req.empty();
+    if (c->cfg.nominated_all) {
+      if (!p.pt_pre) c->pod_table_precompile(p);
+      nm.pre = p.pt_pre;
+      nm.ns = c->ns_id(p.ns);
+    }
   }
   nominated.emplace(p.uid, std::move(nm));
 }
@@ -1759,6 +1788,7 @@ void Engine::nom_prepare() {
     if (ix >= 0) ents.push_back({ix, &kv.first, &kv.second});
   }
   nom_active_ = !ents.empty();
+  nom_nrec_ = (int32_t)ents.size();
   nom_host_.clear();
   if (!nom_active_) return;
   std::sort(ents.begin(), ents.end(), [](const Ent& a, const Ent& b) {
@@ -1788,6 +1818,46 @@ void Engine::nom_prepare() {
     for (const auto& sv : nm.scalar) scs.push_back(ScalarReq{sv.first, 0, sv.second});
     nom_index_[*ents[q].uid] = (int32_t)q;
   }
+  // "EvaluateAll": each record's namespace, labels and required anti-affinity terms, as the pod table holds a
+  // bound pod's (k_nom_topo matches them against a marked pod's programs)
+  std::vector<NomTopoRec> topo;
+  std::vector<unsigned long long> lbls;
+  std::vector<NomTerm> terms;
+  std::vector<int32_t> tpool;
+  if (c->cfg.nominated_all) {
+    topo.resize(ents.size());
+    for (size_t q = 0; q < ents.size(); ++q) {
+      const Nominee& nm = *ents[q].nm;
+      NomTopoRec& t = topo[q];
+      t = NomTopoRec{};
+      t.node = ents[q].node;
+      t.ns = nm.ns;
+      t.lbl_lo = (int32_t)lbls.size();
+      t.term_lo = (int32_t)terms.size();
+      if (nm.pre) {
+        lbls.insert(lbls.end(), nm.pre->labels.begin(), nm.pre->labels.end());
+        const int32_t wb = (int32_t)tpool.size();
+        tpool.insert(tpool.end(), nm.pre->words.begin(), nm.pre->words.end());
+        for (const PodTablePre::Term& pt : nm.pre->terms) {
+          if (pt.kind != T_REQ_ANTI) continue;
+          NomTerm nt{};
+          nt.t.owner = (int32_t)q;
+          nt.t.kind = pt.kind;
+          nt.t.weight = pt.weight;
+          nt.t.key = pt.key;
+          nt.t.sel = wb + pt.sel;
+          nt.t.nssel = wb + pt.nssel;
+          nt.t.ns_off = wb + pt.ns_off;
+          nt.t.ns_cnt = pt.ns_cnt;
+          c->ensure_label_slot(pt.key);
+          nt.slot = c->keys[pt.key].slot;
+          terms.push_back(nt);
+        }
+      }
+      t.lbl_cnt = (int32_t)lbls.size() - t.lbl_lo;
+      t.term_cnt = (int32_t)terms.size() - t.term_lo;
+    }
+  }
   for (size_t i = 0; i < N; ++i) head[i + 1] += head[i];
   auto up16 = [](size_t v) { return (v + 15) & ~size_t(15); };
   NomHdr h{};
@@ -1795,7 +1865,21 @@ void Engine::nom_prepare() {
   h.rec_off = (int32_t)up16(sizeof(NomHdr) + head.size() * 4);
   h.port_off = (int32_t)up16((size_t)h.rec_off + recs.size() * sizeof(NomRec));
   h.sc_off = (int32_t)up16((size_t)h.port_off + ports.size() * 4);
-  nom_host_.assign(up16((size_t)h.sc_off + scs.size() * sizeof(ScalarReq)) + 16, 0);
+  size_t end = up16((size_t)h.sc_off + scs.size() * sizeof(ScalarReq));
+  if (!topo.empty()) {
+    h.topo_off = (int32_t)end;
+    h.lbl_off = (int32_t)up16((size_t)h.topo_off + topo.size() * sizeof(NomTopoRec));
+    h.term_off = (int32_t)up16((size_t)h.lbl_off + lbls.size() * 8);
+    h.tpool_off = (int32_t)up16((size_t)h.term_off + terms.size() * sizeof(NomTerm));
+    end = up16((size_t)h.tpool_off + tpool.size() * 4);
+  }
+  nom_host_.assign(end + 16, 0);
+  if (!topo.empty()) {
+    std::memcpy(nom_host_.data() + h.topo_off, topo.data(), topo.size() * sizeof(NomTopoRec));
+    if (!lbls.empty()) std::memcpy(nom_host_.data() + h.lbl_off, lbls.data(), lbls.size() * 8);
+    if (!terms.empty()) std::memcpy(nom_host_.data() + h.term_off, terms.data(), terms.size() * sizeof(NomTerm));
+    if (!tpool.empty()) std::memcpy(nom_host_.data() + h.tpool_off, tpool.data(), tpool.size() * 4);
+  }
   std::memcpy(nom_host_.data(), &h, sizeof(h));
   std::memcpy(nom_host_.data() + sizeof(NomHdr), head.data(), head.size() * 4);
   std::memcpy(nom_host_.data() + h.rec_off, recs.data(), recs.size() * sizeof(NomRec));
@@ -2658,15 +2742,19 @@ int Engine::run_batch(const std::vector<const PodSpec*>& pods, const std::vector
     const PodDesc& hd = *reinterpret_cast<const PodDesc*>(cp[i].blob.data());
     const bool lds = cp[i].blob.size() <= (size_t)kBlobLds;
     if (hd.flags & DF_AGGREGATE) HIPCHK(launch_aggregate(m, bv, i, hd, s));
-    if (hd.flags & DF_NOMINATED) HIPCHK(launch_nominated(m, bv, i, s));  // evaluateNominatedNode (counts ready)
-    if (hd.flags & DF_OB) HIPCHK(launch_ob_hint(m, bv, i, s));  // GetNodeHint (its counts are ready)
+    // a marked pod with a nominee table staged (nominatedPods "EvaluateAll"): the nominees' deltas, then the
+    // two-pass instances (the kernel boundary orders k_nom_topo before every reader of its rows)
+    const bool nt = (hd.flags & DF_NOM_TOPO) && m.nom != nullptr;
+    if (nt) HIPCHK(launch_nom_topo(m, bv, i, hd, nom_nrec_, s));
+    if (hd.flags & DF_NOMINATED)  // evaluateNominatedNode (counts ready)
+      HIPCHK(nt ? launch_nominated_nt(m, bv, i, s) : launch_nominated(m, bv, i, s));
+    if (hd.flags & DF_OB)  // GetNodeHint (its counts are ready)
+      HIPCHK(nt ? launch_ob_hint_nt(m, bv, i, s) : launch_ob_hint(m, bv, i, s));
     const bool t = stride > 0 && i % stride == 0;
-    if (t) {
-      HIPCHK(launch_filter_score(m, bv, i, s, tev[2 * (size_t)timed], tev[2 * (size_t)timed + 1], 0, -1, lds));
-      timed++;
-    } else {
-      HIPCHK(launch_filter_score(m, bv, i, s, nullptr, nullptr, 0, -1, lds));
-    }
+    hipEvent_t te0 = t ? tev[2 * (size_t)timed] : nullptr, te1 = t ? tev[2 * (size_t)timed + 1] : nullptr;
+    if (nt) HIPCHK(launch_filter_score_nt(m, bv, i, s, te0, te1, lds));
+    else HIPCHK(launch_filter_score(m, bv, i, s, te0, te1, 0, -1, lds));
+    if (t) timed++;
     if (hd.flags & DF_ROTDEV) HIPCHK(launch_sample(m, bv, i, (hd.flags & DF_SAMPLE) != 0, s));
     if (hd.score_mask & (1u << P_PTS)) HIPCHK(launch_pts_score(m, bv, i, s));
     HIPCHK(launch_select(m, bv, i, s, lds));

@@ -229,7 +229,8 @@ struct Config {
                                 // between calls, fed through a host-pinned pod ring ("residentLoop")
   bool agg_loop = true;         // runs of PTS/IPA pods go through k_agg_loop (with persistent_loop)
   int agg_debug = 0;            // AggView::debug (diagnostic)
-  bool nominated_evaluate = false;  // "nominatedPods": "Evaluate" (default "Refuse"), DESIGN.md §4.10
+  bool nominated_evaluate = false;  // "nominatedPods": "Evaluate" or "EvaluateAll" (default "Refuse"), DESIGN.md §4.10
+  bool nominated_all = false;       // "EvaluateAll": also the pairs whose spread / affinity counts the nominees move
   // resident loops: relay the doorbell through device memory from this many workgroups on (one PCIe poller instead
   // of G; round 6, profiles/r06d_resident_ab.txt: C2's 40 workgroups 19.8 -> 14.8 us per call, DTS's 20 27.0 -> 25.3)
   int ring_relay_min = 2;
@@ -552,6 +553,10 @@ class Engine {
     std::vector<std::pair<int32_t, int64_t>> scalar;     // (mirror column, quantity)
     std::vector<uint32_t> ports;                         // host-port ids (Cluster::port_id)
     bool req_anti = false;                               // a required pod anti-affinity term
+    // "EvaluateAll": what PodTopologySpread's / InterPodAffinity's AddPod read of it -- namespace id and the pod
+    // table's precompiled entry (interned label set, affinity terms; Cluster::pod_table_precompile)
+    int32_t ns = 0;
+    std::shared_ptr<const PodTablePre> pre;
   };
   std::unordered_map<std::string, Nominee> nominated;
   void nominate(const PodSpec& p);        // AddNominatedPod / UpdateNominatedPod (none named: forgotten)
@@ -562,8 +567,11 @@ class Engine {
   // nominees could move a topology count the pod's Filter reads: the pod has (a) a DoNotSchedule spread
   // constraint or (b) a required pod (anti-)affinity term, or (c) one of the nominees has a required
   // anti-affinity term.  Refused before anything runs; err names the pod and the condition.
-  int check_nominations(const std::vector<const PodSpec*>& pods);
-  bool nom_evaluate() const;              // config nominatedPods "Evaluate"
+  // "EvaluateAll": a scheduling call (preempt false) is not refused for (a)-(c); its pods in one of those pairs are
+  // marked instead (nom_marked_, DF_NOM_TOPO at compile: the launch path's two-pass instances).  ksg_preempt
+  // stays refused.
+  int check_nominations(const std::vector<const PodSpec*>& pods, bool preempt = false);
+  bool nom_evaluate() const;              // config nominatedPods "Evaluate" / "EvaluateAll"
   bool nom_owner(const PodSpec& p) const { return nominated.count(p.uid) != 0; }
   // The nominee table.  nom_prepare (before a call's first compile): the host copy, rebuilt when the nominator or
   // the snapshot's node list changed -- records grouped by snapshot index, by priority descending within a node;
@@ -692,6 +700,8 @@ class Engine {
   std::vector<uint8_t> nom_host_;
   std::unordered_map<std::string, int32_t> nom_index_;  // uid -> its record (nominees on snapshot nodes)
   bool nom_dirty_ = true, nom_upload_ = false, nom_active_ = false;
+  int32_t nom_nrec_ = 0;                                // records staged (the delta rows of a marked pod)
+  std::unordered_set<const PodSpec*> nom_marked_;       // check_nominations: the call's pods in a pair (a)-(c)
   uint64_t nom_list_gen_ = ~0ull;
   DevBuf d_vsc;  // preemption: the pods' requests of the preemptor's extended resources + the per-node scratch
   std::vector<PRec> h_seg;

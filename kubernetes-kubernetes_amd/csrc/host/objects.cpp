@@ -897,11 +897,12 @@ bool decode_config(const char* p, size_t n, Config* c, std::string* err) {
     c->agg_debug = (int)d.num(r, "aggLoopDebug", 0);
     if (d.present(r, "nominatedPods")) {  // other pods' nominations: refuse the call, or filter with them added
       const std::string np = d.str(r, "nominatedPods");
-      if (np != "Refuse" && np != "Evaluate") {
-        *err = "nominatedPods: Unsupported value \"" + np + "\" (\"Refuse\" or \"Evaluate\")";
+      if (np != "Refuse" && np != "Evaluate" && np != "EvaluateAll") {
+        *err = "nominatedPods: Unsupported value \"" + np + "\" (\"Refuse\", \"Evaluate\" or \"EvaluateAll\")";
         return false;
       }
-      c->nominated_evaluate = np == "Evaluate";
+      c->nominated_evaluate = np != "Refuse";
+      c->nominated_all = np == "EvaluateAll";
     }
     c->ring_relay_min = (int)d.num(r, "ringRelayMinWorkgroups", 2);
     c->debug_give_up_at = (int)d.num(r, "debugLoopGiveUpAt", -1);
