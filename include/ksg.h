@@ -137,6 +137,7 @@ typedef struct ksg_eval_out {
  *    "podTopologySpread": {"defaultingType": "System" | "List",     (PodTopologySpreadArgs)
  *                          "defaultConstraints": [<v1.TopologySpreadConstraint without labelSelector>]},
  *    "nominatedPods": "Refuse" | "Evaluate" | "EvaluateAll",   (other pods' nominations, see ksg_add_nominated_pod)
+ *    "preemptNominatedPods": "Refuse" | "EvaluateAll",         (ksg_preempt under them, see ksg_add_nominated_pod)
  *    "device": 0, "distributed": {"worldSize": 1, "rank": 0, "ncclId": "<hex>"}}
  * Absent keys take the upstream defaults.  Returns NULL on failure (ksg_create_error()). */
 ksg_ctx *ksg_create(const char *config_json, size_t len);
@@ -261,9 +262,19 @@ int ksg_forget(ksg_ctx *ctx, int32_t handle);
  *                       without them, returned Skip runs in neither pass), and, if that passes, as the node is;
  *                       the first failing status is the node's.  The nominator then also keeps each nominated
  *                       pod's namespace, labels and required anti-affinity terms.  Such pods take the per-pod
- *                       launches rather than a persistent loop.  ksg_preempt is still refused for (a)-(c).
+ *                       launches rather than a persistent loop.  ksg_preempt is still refused for (a)-(c),
+ *                       unless "preemptNominatedPods" (below) says otherwise.
  * Any other value fails ksg_create (an invalid argument), and so do "Evaluate" and "EvaluateAll" on a node-sharded
- * context. */
+ * context.
+ * The ksg_create key "preemptNominatedPods" selects what ksg_preempt does for a preemptor in a pair (a)-(c):
+ *   "Refuse" (default)  KSG_ENOTSUP, as above.
+ *   "EvaluateAll"       valid only with "nominatedPods": "EvaluateAll" (ksg_create fails otherwise, naming both
+ *                       keys).  Every filter call of SelectVictimsOnNode's dry run -- after all potential victims
+ *                       are removed, and after each reprieve -- is the two passes above on the node as the dry run
+ *                       holds it: the nominated pods (never victims) added together with their AddPod on top of the
+ *                       victims' RemovePod / AddPod, then, if that passes, the node without them.  A victim is
+ *                       reprieved only if both pass.  The potential nodes are those of the two-pass statuses.
+ * Any other value fails ksg_create. */
 int ksg_add_nominated_pod(ksg_ctx *ctx, const char *pod_json, size_t len);
 int ksg_delete_nominated_pod(ksg_ctx *ctx, const char *uid);
 

@@ -5308,6 +5308,13 @@ __global__ __launch_bounds__(kBlock) void k_nom_topo(MirrorView m, BatchView b, 
   if (ex) add(d.n_ptsf + 1);
 }
 
+// Where the code object's .text starts.  The four two-pass dry-run kernels (k_preempt / k_preempt_seg, NT) added
+// 5 KiB of metadata, symbols and kernel descriptors in front of .text, which moved every kernel by 0x1400 bytes;
+// k_sched_loop, byte for byte the same code, then took 4.23 us per pod instead of 4.18 in bench.py's default
+// workload (profiles/nominated_preempt_ab.txt).  These read-only bytes make the move a whole 64 KiB, which keeps
+// every kernel's address modulo 4, 8 and 64 KiB where it was.  Nothing reads them.
+__device__ __attribute__((used)) const unsigned char k_text_phase_pad[0xEBE0] = {};
+
 }  // namespace ksg
 
 // ---- host-side launchers (C++ linkage, called by the host library) ------------------------------
@@ -6258,8 +6265,105 @@ __device__ __forceinline__ bool preempt_nominees(const MirrorView& m, const uint
   return g.port;
 }
 
-// Host-staged victims (PNode / PVictim: the host sorted them and grouped them by PDB violation)
+// Pass 1 of RunFilterPluginsWithNominatedPods inside the dry run, for a marked preemptor (config
+// preemptNominatedPods "EvaluateAll"): the PreFilter state clone as PreemptTopo holds it -- the victims' RemovePod /
+// AddPod -- with the AddPod of every pod in G(p, i) on top, node i's delta row (k_nom_topo), as NomTopo puts it on
+// ArenaTopo.  Everything moves at node i's own topology values only, so the row adds to the tracked own-domain
+// counts: a count asked for by its histogram base gets the row's words of that histogram; the constraint minimum is
+// min(cnt0 + victims' delta + row[c], excl(c)); affinityCounts is not empty if the cycle's totals with the victims'
+// deltas are not, or a nominee matches all the terms (row[n_ptsf]); antiAffinityCounts likewise.
 template <class S>
+struct PreemptNomTopo {
+  const PreemptTopo<S>& p;
+  const uint8_t* base;
+  const PodDesc& d;
+  const unsigned long long* row;  // node i's delta row
+  __device__ __forceinline__ int64_t cnt(int32_t hist_base, int32_t lref, int32_t v, int ls) const {
+    int64_t x = p.cnt(hist_base, lref, v, ls);
+    const PtsCons* cs = at<PtsCons>(base, d.ptsf_off);
+    for (int32_t c = 0; c < d.n_ptsf; ++c)
+      if (cs[c].hist_base == hist_base) x += (int64_t)row[c];
+    const IpaTerm* ra = at<IpaTerm>(base, d.raff_off);
+    bool aff = false;
+    for (int32_t k = 0; k < d.n_raff; ++k) aff |= ra[k].hist_base == hist_base;
+    if (aff) x += (int64_t)row[d.n_ptsf];
+    const IpaTerm* rn = at<IpaTerm>(base, d.ranti_off);
+    for (int32_t k = 0; k < d.n_ranti; ++k)
+      if (rn[k].hist_base == hist_base) x += (int64_t)row[d.n_ptsf + 2 + k];
+    return x;
+  }
+  __device__ __forceinline__ int64_t pmin(int c) const {
+    int64_t r = p.a.pmin(c);
+    const S& s = p.s;
+    auto own = [&](int k) {
+      const int64_t o = s.cnt0(k) + s.dlt(k) + (int64_t)row[k];
+      r = o < s.excl(k) ? o : s.excl(k);
+    };
+    if constexpr (S::kWide) {
+      if (c < p.nc && s.hb(c) >= 0) own(c);
+    } else {
+      each_k<S>(p.nc, [&](int k) {
+        if (k == c && s.hb(k) >= 0) own(k);
+      });
+    }
+    return r;
+  }
+  __device__ __forceinline__ uint32_t pndom(int c) const { return p.pndom(c); }
+  __device__ __forceinline__ uint32_t any() const {
+    uint32_t x = p.any();
+    if (row[d.n_ptsf]) x |= 1u;
+    for (int32_t k = 0; k < d.n_ranti; ++k)
+      if (row[d.n_ptsf + 2 + k]) x |= 2u;
+    return x;
+  }
+};
+// preempt_nominees for the two-pass instances: *row gets node i's delta row for the dry run's pass 1, nullptr: one
+// pass (the pod is not marked, or G(p, i) is empty)
+__device__ __forceinline__ bool preempt_nominees_nt(const MirrorView& m, const BatchView& b, const uint8_t* base,
+                                                    const PodDesc& d, int i, NodeCore* nc, int64_t* sreq,
+                                                    const unsigned long long** row) {
+  *row = nullptr;
+  if (m.nom == nullptr || !(nc->flags & NF_NOMINEES)) return false;
+  const NomG g = nom_gather(m, base, d, i);
+  *nc = nom_core(*nc, g);
+  if (sreq) {
+    const ScalarReq* sr = at<ScalarReq>(base, d.scalar_off);
+    for (int k = 0; k < d.n_scalar; ++k) sreq[k] += nom_scalar(m, d, g, sr[k].slot);
+  }
+  if ((d.flags & DF_NOM_TOPO) && g.pods > 0)
+    *row = b.arena + d.nom_rows + (size_t)nom_head(m.nom)[i] * (size_t)nom_row_words(d.n_ptsf, d.n_ranti);
+  return g.port;
+}
+// One filter call of SelectVictimsOnNode (the all-victims-removed check, or a reprieve) on the dry run's state:
+// NodePorts / NodeResourcesFit on the core (G already in it, preempt_nominees), then PodTopologySpread /
+// InterPodAffinity on the tracked counts -- topo false: no count moved since a call that passed them, and they pass
+// again.  With a row the step is RunFilterPluginsWithNominatedPods' two passes (framework.go:1211-1294).  Pass 1:
+// fit / ports on core + G and the topology filters through PreemptNomTopo, then the nominees' anti-affinity terms
+// against the preemptor (row[n_ptsf + 1]) unless InterPodAffinity's PreFilter skipped.  Pass 2, if that passed: the
+// topology filters on the counts without G (fit / ports are monotone in the pods added, so they pass without G).
+// Neither pass is monotone in the topology filters; the step's status is pass 1's failure, else pass 2's.
+// (The one-pass instances keep this sequence spelled out at its four places: as a call of this function they
+// allocated registers differently, and they are to stay the kernels they were.)
+template <class S>
+__device__ __forceinline__ uint32_t preempt_step(const MirrorView& m, const NodeCore& nc, const int64_t* sreq,
+                                                 const int64_t* add, const uint8_t* base, const PodDesc& d, int i,
+                                                 bool port, const TopoTrack<S>& T, bool topo,
+                                                 const unsigned long long* row) {
+  uint32_t st = preempt_node_filters(m, nc, sreq, add, base, d, i, port);
+  if (st != 0 || !topo) return st;
+  if (row != nullptr) {
+    const PreemptNomTopo<S> v{T.tp, base, d, row};
+    st = topo_filters(m, base, d, i, v, 0);
+    const bool ipa = ((d.filter_mask >> P_IPA) & 1u) && (d.n_raff > 0 || d.n_ranti > 0 || (T.tp.a.any() & 4u));
+    if (st == 0 && ipa && row[d.n_ptsf + 1]) st = pack_status(C_UNSCHED, P_IPA, KSG_R_IPA_EXISTING_ANTI);
+    if (st != 0) return st;
+  }
+  return topo_filters(m, base, d, i, T.tp, 0);
+}
+
+// Host-staged victims (PNode / PVictim: the host sorted them and grouped them by PDB violation).  NT: the instance
+// a marked preemptor runs (both passes on nodes with nominees, preempt_step).
+template <class S, bool NT = false>
 __global__ __launch_bounds__(kBlock) void k_preempt(MirrorView m, BatchView b, int pod, const PNode* pn,
                                                     const PVictim* pv, uint8_t* vout, POut* out, int all_nodes,
                                                     PreemptIn in) {
@@ -6289,7 +6393,10 @@ __global__ __launch_bounds__(kBlock) void k_preempt(MirrorView m, BatchView b, i
   NodeCore nc = load_core(m, i);
   int64_t* sreq = preempt_sreq(m, base, d, in, i);
   const int ns = d.n_scalar;
-  const bool nom_port = preempt_nominees(m, base, d, i, &nc, sreq);
+  [[maybe_unused]] const unsigned long long* row = nullptr;
+  bool nom_port;
+  if constexpr (NT) nom_port = preempt_nominees_nt(m, b, base, d, i, &nc, sreq, &row);
+  else nom_port = preempt_nominees(m, base, d, i, &nc, sreq);
   TopoTrack<S> T;
   topo_track_init(m, b, pod, base, d, i, in, T, &o.flags);
   const PVictim* v = pv + nd.voff;
@@ -6304,8 +6411,13 @@ __global__ __launch_bounds__(kBlock) void k_preempt(MirrorView m, BatchView b, i
   }
   nc.npods -= nd.vcnt;
   bool port = (nd.flags & PN_BASE_PORT) != 0 || nom_port;
-  uint32_t st = preempt_node_filters(m, nc, sreq, nullptr, base, d, i, port);
-  if (st == 0) st = topo_filters(m, base, d, i, T.tp, 0);
+  uint32_t st;
+  if constexpr (NT) {
+    st = preempt_step(m, nc, sreq, nullptr, base, d, i, port, T, true, row);
+  } else {
+    st = preempt_node_filters(m, nc, sreq, nullptr, base, d, i, port);
+    if (st == 0) st = topo_filters(m, base, d, i, T.tp, 0);
+  }
   o.st = st;
   if (st == 0) {
     for (int q = 0; q < nd.vcnt; ++q) {  // reprieve in the host's order (:331-343)
@@ -6319,8 +6431,13 @@ __global__ __launch_bounds__(kBlock) void k_preempt(MirrorView m, BatchView b, i
       const bool tpo = port || (x.flags & PV_PORT) != 0;
       // tried back: the counts move now and move back if the preemptor no longer fits
       const bool mv = moves && topo_victim(m, base, d, in, T, x.slot, +1);
-      bool fits = preempt_node_filters(m, t, sreq, add, base, d, i, tpo) == 0;
-      if (fits && mv) fits = topo_filters(m, base, d, i, T.tp, 0) == 0;
+      bool fits;
+      if constexpr (NT) {
+        fits = preempt_step(m, t, sreq, add, base, d, i, tpo, T, mv, row) == 0;
+      } else {
+        fits = preempt_node_filters(m, t, sreq, add, base, d, i, tpo) == 0;
+        if (fits && mv) fits = topo_filters(m, base, d, i, T.tp, 0) == 0;
+      }
       if (fits) {
         nc = t;
         if (sreq)
@@ -6339,10 +6456,16 @@ __global__ __launch_bounds__(kBlock) void k_preempt(MirrorView m, BatchView b, i
 }
 
 hipError_t launch_preempt(const MirrorView& m, const BatchView& b, int pod, const PNode* pn, const PVictim* pv,
-                          uint8_t* vout, POut* out, int all_nodes, const PreemptIn& in, hipStream_t s) {
+                          uint8_t* vout, POut* out, int all_nodes, const PreemptIn& in, bool nt, hipStream_t s) {
   const int nb = (m.n + kBlock - 1) / kBlock;
   if (nb == 0) return hipSuccess;
-  if (in.wide)
+  if (nt && in.wide)
+    hipLaunchKernelGGL((k_preempt<PreemptWide, true>), dim3(nb), dim3(kBlock), 0, s, m, b, pod, pn, pv, vout, out,
+                       all_nodes, in);
+  else if (nt)
+    hipLaunchKernelGGL((k_preempt<PreemptRegs, true>), dim3(nb), dim3(kBlock), 0, s, m, b, pod, pn, pv, vout, out,
+                       all_nodes, in);
+  else if (in.wide)
     hipLaunchKernelGGL(k_preempt<PreemptWide>, dim3(nb), dim3(kBlock), 0, s, m, b, pod, pn, pv, vout, out, all_nodes, in);
   else
     hipLaunchKernelGGL(k_preempt<PreemptRegs>, dim3(nb), dim3(kBlock), 0, s, m, b, pod, pn, pv, vout, out, all_nodes, in);
@@ -6354,7 +6477,7 @@ hipError_t launch_preempt(const MirrorView& m, const BatchView& b, int pod, cons
 // victims (the segment suffix below the preemptor's priority), filterPodsWithPDBViolation
 // (default_preemption.go:406-452: selector programs against the pod table's labels, budgets in
 // registers), the victims' host-port conflicts and the node's remaining conflicting ports.
-template <class S>
+template <class S, bool NT = false>
 __global__ __launch_bounds__(kBlock) void k_preempt_seg(MirrorView m, BatchView b, int pod, PreemptView pv) {
   const int i = (int)blockIdx.x * kBlock + (int)threadIdx.x;
   if (i >= m.n) return;
@@ -6429,7 +6552,9 @@ __global__ __launch_bounds__(kBlock) void k_preempt_seg(MirrorView m, BatchView 
     }
   NodeCore nc = load_core(m, i);
   int64_t* sreq = preempt_sreq(m, base, d, in, i);
-  port |= preempt_nominees(m, base, d, i, &nc, sreq);
+  [[maybe_unused]] const unsigned long long* row = nullptr;
+  if constexpr (NT) port |= preempt_nominees_nt(m, b, base, d, i, &nc, sreq, &row);
+  else port |= preempt_nominees(m, base, d, i, &nc, sreq);
   auto vsc = [&](const PRec& x) -> const int64_t* {  // the victim's request of the preemptor's scalars
     return sreq && (x.flags & PR_SCALAR) ? in.vsc + (size_t)x.slot * ns : nullptr;
   };
@@ -6443,8 +6568,13 @@ __global__ __launch_bounds__(kBlock) void k_preempt_seg(MirrorView m, BatchView 
     moves |= topo_victim(m, base, d, in, T, r[q].slot, -1);
   }
   nc.npods -= cnt - first;
-  uint32_t st = preempt_node_filters(m, nc, sreq, nullptr, base, d, i, port);
-  if (st == 0) st = topo_filters(m, base, d, i, T.tp, 0);
+  uint32_t st;
+  if constexpr (NT) {
+    st = preempt_step(m, nc, sreq, nullptr, base, d, i, port, T, true, row);
+  } else {
+    st = preempt_node_filters(m, nc, sreq, nullptr, base, d, i, port);
+    if (st == 0) st = topo_filters(m, base, d, i, T.tp, 0);
+  }
   o.st = st;
   unsigned long long vm0 = 0ull, vm1 = 0ull, vv0 = 0ull, vv1 = 0ull;
   if (st == 0) {
@@ -6461,8 +6591,13 @@ __global__ __launch_bounds__(kBlock) void k_preempt_seg(MirrorView m, BatchView 
         const int64_t* add = vsc(x);
         const bool tpo = port || conf(x.port[0]) || conf(x.port[1]);
         const bool mv = moves && topo_victim(m, base, d, in, T, x.slot, +1);
-        bool fits = preempt_node_filters(m, t, sreq, add, base, d, i, tpo) == 0;
-        if (fits && mv) fits = topo_filters(m, base, d, i, T.tp, 0) == 0;
+        bool fits;
+        if constexpr (NT) {
+          fits = preempt_step(m, t, sreq, add, base, d, i, tpo, T, mv, row) == 0;
+        } else {
+          fits = preempt_node_filters(m, t, sreq, add, base, d, i, tpo) == 0;
+          if (fits && mv) fits = topo_filters(m, base, d, i, T.tp, 0) == 0;
+        }
         if (fits) {
           nc = t;
           if (add)
@@ -6663,10 +6798,15 @@ hipError_t launch_preempt_pick(const PSegOut* out, int n, int64_t offset, int64_
   return hipGetLastError();
 }
 
-hipError_t launch_preempt_seg(const MirrorView& m, const BatchView& b, int pod, const PreemptView& pv, hipStream_t s) {
+hipError_t launch_preempt_seg(const MirrorView& m, const BatchView& b, int pod, const PreemptView& pv, bool nt,
+                              hipStream_t s) {
   const int nb = (m.n + kBlock - 1) / kBlock;
   if (nb == 0) return hipSuccess;
-  if (pv.in.wide)
+  if (nt && pv.in.wide)
+    hipLaunchKernelGGL((k_preempt_seg<PreemptWide, true>), dim3(nb), dim3(kBlock), 0, s, m, b, pod, pv);
+  else if (nt)
+    hipLaunchKernelGGL((k_preempt_seg<PreemptRegs, true>), dim3(nb), dim3(kBlock), 0, s, m, b, pod, pv);
+  else if (pv.in.wide)
     hipLaunchKernelGGL(k_preempt_seg<PreemptWide>, dim3(nb), dim3(kBlock), 0, s, m, b, pod, pv);
   else
     hipLaunchKernelGGL(k_preempt_seg<PreemptRegs>, dim3(nb), dim3(kBlock), 0, s, m, b, pod, pv);

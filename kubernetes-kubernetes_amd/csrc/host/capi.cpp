@@ -438,7 +438,7 @@ int ksg_preempt(ksg_ctx* ctx, int32_t handle, const char* args_json, size_t args
     // node-sharded contexts: every rank holds the whole mirror and pod table, so each rank runs the
     // PostFilter over every node by itself (no exchange) and returns the identical choice
     // (SelectVictimsOnNode filters with the nominated pods too: refused likewise -- under "EvaluateAll" as well,
-    // where every reprieve step would need both passes)
+    // where every reprieve step needs both passes, unless preemptNominatedPods "EvaluateAll" marks the preemptor)
     if (const int rn = ctx->engine->check_nominations({&it->second}, true)) return with_err(ctx, rn);
     if (const int rs = quiesce(ctx)) return rs;
     std::string d;

@@ -1687,7 +1687,9 @@ int Engine::group_launch(GroupReq* req, bool agg, int nwg, int unit) {
 // against the nominator as the call found it.
 // "EvaluateAll" schedules those pairs too: such a pod is marked (DF_NOM_TOPO at compile) and takes the launch path's
 // two-pass instances, k_nom_topo's deltas behind k_aggregate.  A mark is a superset -- a marked pod whose G is empty
-// by its turn finds no record and is evaluated as any other.  ksg_preempt (preempt) stays refused.
+// by its turn finds no record and is evaluated as any other.  ksg_preempt (preempt) stays refused for those pairs
+// unless config preemptNominatedPods is "EvaluateAll": then the preemptor is marked likewise, and every filter call
+// of the dry run (the all-victims-removed check and each reprieve) runs both passes (k_preempt / k_preempt_seg NT).
 int Engine::check_nominations(const std::vector<const PodSpec*>& pods, bool preempt) {
   nom_marked_.clear();
   if (nominated.empty()) return KSG_OK;
@@ -1724,7 +1726,7 @@ int Engine::check_nominations(const std::vector<const PodSpec*>& pods, bool pree
       why = "(b) the pod has a required pod affinity or anti-affinity term, whose counts the nominated pod may move";
     else if (anti)
       why = "(c) the nominated pod has a required pod anti-affinity term, which InterPodAffinity would check against the pod";
-    if (why && c->cfg.nominated_all && !preempt) {
+    if (why && c->cfg.nominated_all && (!preempt || c->cfg.preempt_nominated_all)) {
       nom_marked_.insert(p);
       continue;
     }

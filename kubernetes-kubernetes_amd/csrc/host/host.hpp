@@ -231,6 +231,7 @@ struct Config {
   int agg_debug = 0;            // AggView::debug (diagnostic)
   bool nominated_evaluate = false;  // "nominatedPods": "Evaluate" or "EvaluateAll" (default "Refuse"), DESIGN.md §4.10
   bool nominated_all = false;       // "EvaluateAll": also the pairs whose spread / affinity counts the nominees move
+  bool preempt_nominated_all = false;  // "preemptNominatedPods": "EvaluateAll": ksg_preempt for those pairs too
   // resident loops: relay the doorbell through device memory from this many workgroups on (one PCIe poller instead
   // of G; round 6, profiles/r06d_resident_ab.txt: C2's 40 workgroups 19.8 -> 14.8 us per call, DTS's 20 27.0 -> 25.3)
   int ring_relay_min = 2;
@@ -569,7 +570,8 @@ class Engine {
   // anti-affinity term.  Refused before anything runs; err names the pod and the condition.
   // "EvaluateAll": a scheduling call (preempt false) is not refused for (a)-(c); its pods in one of those pairs are
   // marked instead (nom_marked_, DF_NOM_TOPO at compile: the launch path's two-pass instances).  ksg_preempt
-  // stays refused.
+  // (preempt true) stays refused unless config preemptNominatedPods is "EvaluateAll": then the preemptor is marked
+  // the same way and the dry run takes its two-pass instances (k_preempt / k_preempt_seg NT).
   int check_nominations(const std::vector<const PodSpec*>& pods, bool preempt = false);
   bool nom_evaluate() const;              // config nominatedPods "Evaluate" / "EvaluateAll"
   bool nom_owner(const PodSpec& p) const { return nominated.count(p.uid) != 0; }

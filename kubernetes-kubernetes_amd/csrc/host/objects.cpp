@@ -904,6 +904,19 @@ bool decode_config(const char* p, size_t n, Config* c, std::string* err) {
       c->nominated_evaluate = np != "Refuse";
       c->nominated_all = np == "EvaluateAll";
     }
+    if (d.present(r, "preemptNominatedPods")) {  // ksg_preempt for the pairs that need both passes
+      const std::string np = d.str(r, "preemptNominatedPods");
+      if (np != "Refuse" && np != "EvaluateAll") {
+        *err = "preemptNominatedPods: Unsupported value \"" + np + "\" (\"Refuse\" or \"EvaluateAll\")";
+        return false;
+      }
+      c->preempt_nominated_all = np == "EvaluateAll";
+    }
+    if (c->preempt_nominated_all && !c->nominated_all) {
+      *err = "preemptNominatedPods \"EvaluateAll\" requires nominatedPods \"EvaluateAll\" (the failed cycle's "
+             "statuses are the two-pass ones)";
+      return false;
+    }
     c->ring_relay_min = (int)d.num(r, "ringRelayMinWorkgroups", 2);
     c->debug_give_up_at = (int)d.num(r, "debugLoopGiveUpAt", -1);
     c->loop_wave_map = (int)d.num(r, "loopWaveMap", 0);

@@ -29,8 +29,12 @@ hipError_t launch_aggregate(const MirrorView& m, const BatchView& b, int pod, co
 hipError_t launch_filter_score(const MirrorView& m, const BatchView& b, int pod, hipStream_t s, hipEvent_t t0,
                                hipEvent_t t1, int blk0, int nblk, bool lds);
 hipError_t launch_preempt(const MirrorView& m, const BatchView& b, int pod, const PNode* pn, const PVictim* pv,
-                          uint8_t* vout, POut* out, int all_nodes, const PreemptIn& in, hipStream_t s);
-hipError_t launch_preempt_seg(const MirrorView& m, const BatchView& b, int pod, const PreemptView& pv, hipStream_t s);
+                          uint8_t* vout, POut* out, int all_nodes, const PreemptIn& in, bool nt, hipStream_t s);
+hipError_t launch_preempt_seg(const MirrorView& m, const BatchView& b, int pod, const PreemptView& pv, bool nt,
+                              hipStream_t s);
+hipError_t launch_nom_topo(const MirrorView& m, const BatchView& b, int pod, const PodDesc& d, int nrec, hipStream_t s);
+hipError_t launch_filter_score_nt(const MirrorView& m, const BatchView& b, int pod, hipStream_t s, hipEvent_t t0,
+                                  hipEvent_t t1, bool lds);
 hipError_t launch_pts_minima(const BatchView& b, int pod, int ncons, long long* mm, hipStream_t s);
 hipError_t launch_aff_totals(const BatchView& b, int pod, int nterms, long long* out, hipStream_t s);
 hipError_t launch_preempt_terms(const MirrorView& m, const BatchView& b, int pod, int32_t* contrib, hipStream_t s);
@@ -335,6 +339,9 @@ int Engine::preempt(const PodSpec& p, const char* args_json, size_t args_len, ks
   hipStream_t s = c->stream;
   const MirrorView& m = c->view;
   BatchView bv{};
+  // a marked preemptor (config preemptNominatedPods "EvaluateAll") with a nominee table staged: k_nom_topo's delta
+  // rows behind k_aggregate, the two-pass status pass and the dry run's two-pass instances
+  const bool nt = (D.flags & DF_NOM_TOPO) && m.nom != nullptr;
   auto stage_pod = [&]() -> int {  // the preemptor's program + stats, then the cycle's statuses
     if ((rc = ensure_scratch(cp.blob.size(), 1, true, cp.arena_words))) return rc;
     hp = (uint8_t*)h_pinned;
@@ -351,7 +358,12 @@ int Engine::preempt(const PodSpec& p, const char* args_json, size_t args_len, ks
     PCHK(hipMemcpyAsync(d_stats.p, hs, sizeof(PodStats), hipMemcpyHostToDevice, s));
     bv = bview(1);
     if (D.flags & DF_AGGREGATE) PCHK(launch_aggregate(m, bv, 0, D, s));
-    PCHK(launch_filter_score(m, bv, 0, s, nullptr, nullptr, 0, -1, cp.blob.size() <= (size_t)kBlobLds));
+    if (nt) {  // (the kernel boundary orders k_nom_topo before every reader of its rows)
+      PCHK(launch_nom_topo(m, bv, 0, D, nom_nrec_, s));
+      PCHK(launch_filter_score_nt(m, bv, 0, s, nullptr, nullptr, cp.blob.size() <= (size_t)kBlobLds));
+    } else {
+      PCHK(launch_filter_score(m, bv, 0, s, nullptr, nullptr, 0, -1, cp.blob.size() <= (size_t)kBlobLds));
+    }
     return KSG_OK;
   };
   // what both kernels read about the victims beyond Requested (PreemptIn): the cycle's DoNotSchedule minima,
@@ -461,7 +473,7 @@ int Engine::preempt(const PodSpec& p, const char* args_json, size_t args_len, ks
     v.all_nodes = all_nodes ? 1 : 0;
     v.now = now;
     v.in = pin;
-    PCHK(launch_preempt_seg(m, bv, 0, v, s));
+    PCHK(launch_preempt_seg(m, bv, 0, v, nt, s));
     if ((rc = ensure(d_pick, sizeof(PickOut) + 4 * (size_t)N + 64))) return rc;
     PickOut* d_po = (PickOut*)d_pick.p;
     PCHK(launch_preempt_pick((const PSegOut*)d_psout.p, N, offset_in, pct, absn, (int32_t*)(d_po + 1), d_po, s));
@@ -545,7 +557,7 @@ int Engine::preempt(const PodSpec& p, const char* args_json, size_t args_len, ks
       uint8_t* d_vo = dp + pn_b + pv_b + po_b;
       PCHK(hipMemcpyAsync(d_pn, pn.data(), pn_b, hipMemcpyHostToDevice, s));
       if (V) PCHK(hipMemcpyAsync(d_pv, pv.data(), pv_b, hipMemcpyHostToDevice, s));
-      PCHK(launch_preempt(m, bv, 0, d_pn, d_pv, d_vo, d_po, all_nodes ? 1 : 0, pin, s));
+      PCHK(launch_preempt(m, bv, 0, d_pn, d_pv, d_vo, d_po, all_nodes ? 1 : 0, pin, nt, s));
       PCHK(hipMemcpyAsync(pout.data(), d_po, po_b, hipMemcpyDeviceToHost, s));
       if (V) PCHK(hipMemcpyAsync(vo.data(), d_vo, vo_b, hipMemcpyDeviceToHost, s));
       if ((rc = finish_device())) return rc;
