@@ -409,6 +409,12 @@ int ksg_debug_relayouts(const ksg_ctx *ctx, uint64_t *full, uint64_t *gather);
  * Both stay 0 in a healthy run; the tests assert it. */
 int ksg_debug_loop_stats(const ksg_ctx *ctx, uint64_t *give_ups, uint64_t *retries);
 
+/* k_sched_loop's lean selection path (config "loopLeanSelect", default true): the pods handed to
+ * k_sched_loop since the context was created, while the key was on, that the path takes (*lean: compiled with raw
+ * TaintToleration and NodeAffinity scores of 0 on every node, and scoring) and the others (*general).  Counted on
+ * the host; both stay 0 with the key off. */
+int ksg_debug_lean_pods(const ksg_ctx *ctx, uint64_t *lean, uint64_t *general);
+
 /* Parity diagnostic (no device needed): fills out[k] = math.Log(float64(k)) for 0 <= k < n with
  * the table PodTopologySpread's score kernel reads (topologyNormalizingWeight, podtopologyspread/
  * scoring.go:287-299: log(size + 2)).  Returns n. */

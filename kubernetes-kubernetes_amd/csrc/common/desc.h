@@ -671,6 +671,7 @@ struct alignas(128) PodRing {
   alignas(128) unsigned long long patch[kRingSlots][kPatchWords];  // [host] RING_TERMS
 };
 
+enum : int32_t { kLeanA = 1, kLeanP2 = 2, kLeanP1 = 4, kLeanAll = 7 };  // LoopView::lean_select
 struct LoopView {
   int32_t first_pod, npods;  // pods [first_pod, first_pod + npods) of the batch
   int32_t nwg;               // workgroups of this rank (all resident; one per CU at most)
@@ -688,6 +689,10 @@ struct LoopView {
   unsigned long long ring_idle;  // resident mode: s_memrealtime ticks (100 MHz) without a pod before leaving
   int32_t ring_ahead;        // resident mode: evaluate the next pod's phase 1 ahead of its doorbell (config residentAhead)
   int32_t split_eval;        // batch runs, unsharded, 128-node units: the split instance (config loopSplitEval)
+  // DF_RAW0 pods (config loopLeanSelect; 0: off, true: all parts): kLeanA the selection wave sweeps and reduces
+  // exchange A's counts granule only, kLeanP2 its phase 2 adds one constant, kLeanP1 phase 1 publishes its maxima
+  // without reducing them -- the parts are apart only to be measured apart
+  int32_t lean_select;
   // resident mode with many workgroups: workgroup 0 alone polls the host's ctl and relays the word through
   // device memory (relay[0]), where the others poll (nullptr: every workgroup polls the host)
   unsigned long long* relay;

@@ -2441,10 +2441,18 @@ __device__ __forceinline__ void sched_loop_body(const MirrorView& m, const Batch
     }
     return wave_sum_u32(c);
   };
-  auto publish_partials = [&](int par) __attribute__((always_inline)) {
-    s_tm[par][t] = t_mt;
-    s_tn[par][t] = t_mn;
-    const unsigned long long mt = wave_max_u64(t_mt), mn = wave_max_u64(t_mn);
+  // raw0 (loopLeanSelect, a DF_RAW0 pod): every raw score is 0, so a wave's maxima are enc(0) when it has a
+  // feasible node, else 0 -- no reduction, and no per-slot maxima (only the helper's general branch reads them)
+  auto publish_partials = [&](int par, bool raw0) __attribute__((always_inline)) {
+    unsigned long long mt, mn;
+    if (raw0) {
+      mt = mn = w_cnt > 0 ? enc_i64(0) : 0ull;
+    } else {
+      s_tm[par][t] = t_mt;
+      s_tn[par][t] = t_mn;
+      mt = wave_max_u64(t_mt);
+      mn = wave_max_u64(t_mn);
+    }
     if (lane == 0) {
       s_u[par][0][wave] = w_cnt;
       s_u[par][1][wave] = w_below;
@@ -2512,7 +2520,7 @@ __device__ __forceinline__ void sched_loop_body(const MirrorView& m, const Batch
         record(kk, ne);
       }
     }
-    publish_partials(par);
+    publish_partials(par, (lv.lean_select & kLeanP1) && (d.flags & DF_RAW0));
     if (lane == 0) __hip_atomic_fetch_add(&s_e_done, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
   };
   // SPLIT, the post waves' half of a phase-1 round: the pod in `slot` on each of my nodes as if pod dprev were
@@ -2583,6 +2591,36 @@ __device__ __forceinline__ void sched_loop_body(const MirrorView& m, const Batch
             *knode = kv > *key ? (k0 + kk) * U + v * 64 + lane : *knode;
             *key = kv > *key ? kv : *key;
           }
+          acc += (uint32_t)__popcll(ballot[v]);
+        }
+      }
+    }
+  };
+  // phase 2 of a DF_RAW0 pod that scores (loopLeanSelect): both normalising maxima are 0, so NormalizeScore gives
+  // every feasible node the same addend (`add`: 100 * weight[TaintToleration] when the plugin scores, NodeAffinity
+  // adds 0 -- loop_total with mx_t == mx_n == 0).  Per slot only the ballot and the fixed score are read; positions,
+  // the cut, endn and the key are phase2_half's, bit for bit.
+  auto phase2_lean = [&](uint32_t acc, uint32_t F, uint32_t ps_before, int64_t add, int par, unsigned long long* key,
+                         int* knode, uint32_t cutK, uint32_t gK, int* endn) __attribute__((always_inline)) {
+#pragma unroll
+    for (int kk = 0; kk < kLoopMaxBlk; ++kk) {
+      if (kk < nk) {
+        unsigned long long ballot[NW];
+        int64_t fx[NW];
+#pragma unroll
+        for (int v = 0; v < NW; ++v) {
+          ballot[v] = s_ball[par][kk][v];
+          fx[v] = s_fx[par][kk][v * 64 + lane];
+        }
+#pragma unroll
+        for (int v = 0; v < NW; ++v) {
+          const bool f = ((ballot[v] >> lane) & 1ull) != 0;
+          const uint32_t g = acc + wave_prefix_count(ballot[v], lane);
+          const uint32_t pos = g >= ps_before ? g - ps_before : g + F - ps_before;
+          const unsigned long long kv = f && pos < cutK ? pack_best(fx[v] + add, pos) : 0ull;
+          *endn = f && g == gK ? (k0 + kk) * U + v * 64 + lane : *endn;
+          *knode = kv > *key ? (k0 + kk) * U + v * 64 + lane : *knode;
+          *key = kv > *key ? kv : *key;
           acc += (uint32_t)__popcll(ballot[v]);
         }
       }
@@ -2734,37 +2772,60 @@ __device__ __forceinline__ void sched_loop_body(const MirrorView& m, const Batch
       // ======== selection wave: exchange A, phase 2, exchange B, pre-evaluation, staging ========
       stamp_s(q, 0);  // exchange A of this pod was published at the end of the previous one
       if (kSt && lv.wstamps && lane == 0) lv.wstamps[((size_t)q * G + w) * 8 + 7] = __builtin_amdgcn_s_memrealtime();
-      unsigned long long xa[2][MS];
-      bool ok = gran_sweep<2, MS>(lv, q, 0, xa);
+      // the lean path (loopLeanSelect): a pod that scores and whose raw TaintToleration / NodeAffinity scores are 0
+      // on every node (DF_RAW0) -- exchange A's maxima are enc(0) or 0 whatever the cluster does, so only the counts
+      // granule is swept and reduced, and phase 2 adds one constant.  The flags word is made scalar: one branch
+      // per wave.  Every workgroup still publishes both granules.
+      const uint32_t dflags = (uint32_t)__builtin_amdgcn_readfirstlane((int)d.flags);
+      // (lv.lean_select: kLeanA the sweep and its reduction, kLeanP2 phase 2 -- apart only for measurements)
+      const bool lean = lv.lean_select && (dflags & (DF_RAW0 | DF_NO_SCORE)) == DF_RAW0;
+      bool ok;
       uint32_t F = 0, wp = 0, bf = 0;
       unsigned long long tmax = 0, nmax = 0;
+      if (lean && (lv.lean_select & kLeanA)) {
+        unsigned long long xc[1][MS];
+        ok = gran_sweep<1, MS>(lv, q, 0, xc);
 #pragma unroll
-      for (int r = 0; r < MS; ++r) {
-        const int v = lane + 64 * r;
-        if (v < P) {
-          const uint32_t c = gran_a_count(xa[0][r]);
-          F += c;
-          if (v < gid) wp += c;
-          bf += gran_a_below(xa[0][r]);
-          const unsigned long long tv = gran_a_tp1(xa[1][r]), nv = gran_a_np1(xa[1][r]);
-          tmax = tv > tmax ? tv : tmax;
-          nmax = nv > nmax ? nv : nmax;
+        for (int r = 0; r < MS; ++r) {
+          const int v = lane + 64 * r;
+          if (v < P) {
+            const uint32_t c = gran_a_count(xc[0][r]);
+            F += c;
+            if (v < gid) wp += c;
+            bf += gran_a_below(xc[0][r]);
+          }
         }
+      } else {
+        unsigned long long xa[2][MS];
+        ok = gran_sweep<2, MS>(lv, q, 0, xa);
+#pragma unroll
+        for (int r = 0; r < MS; ++r) {
+          const int v = lane + 64 * r;
+          if (v < P) {
+            const uint32_t c = gran_a_count(xa[0][r]);
+            F += c;
+            if (v < gid) wp += c;
+            bf += gran_a_below(xa[0][r]);
+            const unsigned long long tv = gran_a_tp1(xa[1][r]), nv = gran_a_np1(xa[1][r]);
+            tmax = tv > tmax ? tv : tmax;
+            nmax = nv > nmax ? nv : nmax;
+          }
+        }
+        tmax = wave_max_u64(tmax);
+        nmax = wave_max_u64(nmax);
       }
       F = wave_sum_u32(F);
       const uint32_t ps_before = wave_sum_u32(bf);
       uint32_t acc = wave_sum_u32(wp);  // feasible nodes before my range
-      tmax = wave_max_u64(tmax);
-      nmax = wave_max_u64(nmax);
       stamp_s(q, 1);
 
       // percentageOfNodesToScore (DF_ROTDEV, unsharded): findNodesThatPassFilters keeps the first K
       // feasible nodes of the rotated order and stops at the (K+1)-th (schedule_one.go:809-824)
-      const bool rotd = (d.flags & DF_ROTDEV) != 0;
-      const uint32_t K = rotd ? (uint32_t)d.num_to_find : 0xffffffffu;
+      const bool rotd = (dflags & DF_ROTDEV) != 0;
+      const uint32_t K = rotd ? (uint32_t)__builtin_amdgcn_readfirstlane(d.num_to_find) : 0xffffffffu;
       const bool cut = rotd && F > K;
       const uint32_t gK = cut ? (ps_before + K) % F : 0xffffffffu;  // its global feasible index
-      if (cut && ok && (tmax > 1 || nmax > 1)) {
+      if (!lean && cut && ok && (tmax > 1 || nmax > 1)) {  // (lean: both maxima are 0, the kept ones too)
         // some raw TaintToleration / NodeAffinity score is > 0: NormalizeScore's maxima are over the kept
         // nodes only -- one more exchange (M, at pod index q + kLoopMaxPods) of the kept maxima
         unsigned long long mt = 0, mn = 0, g0, g1;
@@ -2789,10 +2850,19 @@ __device__ __forceinline__ void sched_loop_body(const MirrorView& m, const Batch
       }
 
       // ---- phase 2: positions, NormalizeScore + weights, my range's best packed key
-      const int64_t mx_t = tmax ? (int64_t)tmax - 1 : 0, mx_n = nmax ? (int64_t)nmax - 1 : 0;
       unsigned long long key = 0;
       int knode = -1, endn = -1;
-      if (ok) phase2_half(0, NW, acc, F, ps_before, mx_t, mx_n, d, par, &key, &knode, K, gK, &endn);
+      if (lean && (lv.lean_select & kLeanP2)) {
+        // the pod's constant, uniform: read from the program once, before the block loop
+        const uint32_t sm = (uint32_t)__builtin_amdgcn_readfirstlane((int)d.score_mask);
+        const uint32_t wlo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)d.weight[P_TAINT]);
+        const uint32_t whi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)((uint64_t)d.weight[P_TAINT] >> 32));
+        const int64_t add = ((sm >> P_TAINT) & 1u) ? 100 * (int64_t)(((uint64_t)whi << 32) | wlo) : 0;
+        if (ok) phase2_lean(acc, F, ps_before, add, par, &key, &knode, K, gK, &endn);
+      } else {
+        const int64_t mx_t = tmax ? (int64_t)tmax - 1 : 0, mx_n = nmax ? (int64_t)nmax - 1 : 0;
+        if (ok) phase2_half(0, NW, acc, F, ps_before, mx_t, mx_n, d, par, &key, &knode, K, gK, &endn);
+      }
       const unsigned long long wkey = wave_max_u64(key);
       const unsigned long long hold = __ballot(key == wkey && key != 0ull);
       const int cand = hold ? __builtin_amdgcn_readlane(knode, (int)__builtin_ctzll(hold)) : -1;
@@ -3149,7 +3219,7 @@ __device__ __forceinline__ void sched_loop_body(const MirrorView& m, const Batch
           w_cnt = w_cnt - (uint32_t)__popcll(old) + (uint32_t)__popcll(nbal);
           w_below = w_below - (uint32_t)__popcll(old & bmk) + (uint32_t)__popcll(nbal & bmk);
           if (lane == 0) s_ball[npar][kw][wave] = nbal;
-          publish_partials(npar);
+          publish_partials(npar, (lv.lean_select & kLeanP1) && (nd.flags & DF_RAW0));
           if (lane == 0) publish_a(q + 1, npar);  // the other waves' partials are final since the barrier
         }
       }

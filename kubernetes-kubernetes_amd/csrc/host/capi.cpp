@@ -552,6 +552,13 @@ int ksg_debug_loop_stats(const ksg_ctx* ctx, uint64_t* give_ups, uint64_t* retri
   return KSG_OK;
 }
 
+int ksg_debug_lean_pods(const ksg_ctx* ctx, uint64_t* lean, uint64_t* general) {
+  if (!ctx || !lean || !general) return KSG_EINVAL;
+  *lean = ctx->engine->lean_pods_;
+  *general = ctx->engine->general_pods_;
+  return KSG_OK;
+}
+
 int ksg_debug_log_table(double* out, int32_t n) {
   if (!out || n < 0) return KSG_EINVAL;
   for (int32_t k = 0; k < n; ++k) out[k] = ksg::go_log((double)k);  // as Cluster::upload_pod_table builds it

@@ -2592,9 +2592,11 @@ int Engine::run_batch(const std::vector<const PodSpec*>& pods, const std::vector
       int j = i;
       double rb = 0;
       const int cut = chunk_end(i);
-      while (j < n && j < cut && j - i < kLoopMaxPods && loop_ok(cp[j]))
-        rb += algo_bytes(*reinterpret_cast<const PodDesc*>(cp[j++].blob.data())) *
-              (comm && m.n > 0 ? std::min(1.0, (double)snblk * kBlock / (double)m.n) : 1.0);
+      while (j < n && j < cut && j - i < kLoopMaxPods && loop_ok(cp[j])) {
+        const PodDesc& hd = *reinterpret_cast<const PodDesc*>(cp[j++].blob.data());
+        count_lean(hd);
+        rb += algo_bytes(hd) * (comm && m.n > 0 ? std::min(1.0, (double)snblk * kBlock / (double)m.n) : 1.0);
+      }
       while (lev.size() < 2 * (runs.size() + 1)) {
         hipEvent_t e;
         HIPCHK(hipEventCreate(&e));
@@ -2617,6 +2619,7 @@ int Engine::run_batch(const std::vector<const PodSpec*>& pods, const std::vector
       lv.wave_map = c->cfg.loop_wave_map;
       // the split instance: unsharded 128-node-unit runs without a nominee table (launch_sched_loop)
       lv.split_eval = c->cfg.loop_split_eval && unit == 128 && W == 1 && !comm && m.nom == nullptr ? 1 : 0;
+      lv.lean_select = c->cfg.loop_lean_select;
       lv.diag = diag ? (int32_t*)d_diag.p : nullptr;  // the diagnosing instance (launch_sched_loop)
       lv.wstamps = c->cfg.loop_stamps ? (unsigned long long*)d_stamps.p + (size_t)n * 8 + 64 + (size_t)i * GS * 8 : nullptr;
       // in-process ranks: every rank is past its allocations before any rank's first loop starts
@@ -3603,6 +3606,7 @@ relaunch:
       lv.ring = ring_dev_;
       lv.ring_idle = (unsigned long long)kResidentIdleMs * 100000ull;  // s_memrealtime: 100 MHz
       lv.ring_ahead = c->cfg.resident_ahead ? 1 : 0;
+      lv.lean_select = c->cfg.loop_lean_select;
       if (c->cfg.loop_stamps) {  // per-pod phase stamps (the resident instance writes them in the diagnostic build)
         if ((rc = ensure(d_stamps, (size_t)kLoopMaxPods * 8 * 8))) return fail(rc);
         HIPCHK(hipMemsetAsync(d_stamps.p, 0, (size_t)kLoopMaxPods * 8 * 8, s));
@@ -3694,6 +3698,7 @@ relaunch:
     // the previous call's program but for the slot and the rotation: the loop copies it in LDS (RING_SAME)
     bool same = q > 0 && res_prev_blob_.size() == cp.blob.size() && !(c->cfg.agg_debug & 8);
     const PodDesc& hd = *reinterpret_cast<const PodDesc*>(cp.blob.data());
+    if (!reposted) count_lean(hd);
     if (same) {
       PodDesc& pd = *reinterpret_cast<PodDesc*>(res_prev_blob_.data());
       const PodDesc keep = pd;

@@ -238,7 +238,10 @@ struct Config {
   int first_chunk = 32;         // pods in a pipelined batch's first chunk (the host work before the first launch)
   int loop_wave_map = 0;        // k_sched_loop role-to-wave placement (kWaveMap / kSplitWaveMap in kernels.hip)
   bool loop_split_eval = true;  // k_sched_loop: phase 1's two evaluations on separate waves ("loopSplitEval")
-  bool resident_ahead = true;   // resident loops: the next pod's phase 1 ahead of its doorbell (LoopView, AggView bit 7)
+  // k_sched_loop: the lean path for DF_RAW0 pods ("loopLeanSelect": true / false, or a mask of its parts for
+  // measurements: desc.h kLeanA | kLeanP2 | kLeanP1)
+  int loop_lean_select = kLeanAll;
+  bool resident_ahead = true;  // resident loops: the next pod's phase 1 ahead of its doorbell (LoopView, AggView bit 7)
   int debug_give_up_at = -1;    // diagnostic: the persistent loops give up at this pod of a run
   int loop_wg = 0;              // k_sched_loop workgroups (0: min(node units, CUs, 128))
   int loop_unit = 128;          // k_sched_loop nodes per workgroup unit: 128 (when it fits) or 256 ("loopUnit")
@@ -611,6 +614,13 @@ class Engine {
   bool force_allreduce_ = false;  // run_batch_api's retry: no device exchange
   uint64_t loop_retries_ = 0;   // batches run_batch_api re-ran over the all-reduce path
   uint64_t loop_give_ups_ = 0;  // batches whose persistent loop gave up (forced ones included)
+  // pods handed to k_sched_loop while loopLeanSelect was on: those its lean selection path takes (DF_RAW0 and not
+  // DF_NO_SCORE) and the others (ksg_debug_lean_pods)
+  uint64_t lean_pods_ = 0, general_pods_ = 0;
+  void count_lean(const PodDesc& hd) {
+    if (!c->cfg.loop_lean_select) return;
+    ++((hd.flags & (DF_RAW0 | DF_NO_SCORE)) == DF_RAW0 ? lean_pods_ : general_pods_);
+  }
   int run_plugin(const PodSpec& p, Mode mode, int plugin, const uint8_t* nodes, int32_t* code, uint8_t* codes,
                  uint32_t* reasons, int64_t* raw, int64_t* norm);
   // DefaultPreemption's PostFilter for a pod that failed its cycle (preempt.cpp)

@@ -129,6 +129,17 @@ class Scheduler(Backend):
         self._chk(self.lib.ksg_debug_loop_stats(self.ctx, C.byref(g), C.byref(r)), "loop_stats")
         return g.value, r.value
 
+    def lean_pods(self):
+        """(lean, general): the pods handed to k_sched_loop so far, while loopLeanSelect was on, that its lean
+        selection path takes and that it does not (ksg_debug_lean_pods; bound on first use, so that KSG_LIB may
+        still name a library built before it)."""
+        fn = self.lib.ksg_debug_lean_pods
+        fn.restype = C.c_int
+        fn.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+        a, b = C.c_uint64(), C.c_uint64()
+        self._chk(fn(self.ctx, C.byref(a), C.byref(b)), "lean_pods")
+        return a.value, b.value
+
     def relayouts(self):
         """(full mirror rebuilds, gather re-layouts) so far (ksg_debug_relayouts)."""
         f, g = C.c_uint64(), C.c_uint64()

@@ -1,4 +1,6 @@
-"""Diagnostic: k_sched_loop per-phase stamps and pods/s for several workgroup counts (C2 shape)."""
+"""Diagnostic: k_sched_loop per-phase stamps and pods/s for several workgroup counts (C2 shape).
+   python scripts/loop_probe.py [nodes] [workgroups,...] [hetero|tied] [extra config as JSON]"""
+import json
 import os
 import sys
 import time
@@ -11,9 +13,10 @@ from ksg import synth  # noqa: E402
 nodes_n = int(sys.argv[1]) if len(sys.argv) > 1 else 5000
 wgs = [int(x) for x in (sys.argv[2].split(",") if len(sys.argv) > 2 else ["0"])]
 hetero = len(sys.argv) > 3 and sys.argv[3] == "hetero"
+extra = json.loads(sys.argv[4]) if len(sys.argv) > 4 else {}
 nodes, init, pods = synth.scheduling_basic(nodes_n, 1000, 3000, hetero=hetero)
 for wg in wgs:
-    s = Scheduler({"device": 0, "loopWorkgroups": wg, "loopStamps": True})
+    s = Scheduler(dict({"device": 0, "loopWorkgroups": wg, "loopStamps": True}, **extra))
     for n in nodes:
         s.add_node(n)
     for p in init:
