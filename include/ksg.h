@@ -138,7 +138,8 @@ typedef struct ksg_eval_out {
  *                          "defaultConstraints": [<v1.TopologySpreadConstraint without labelSelector>]},
  *    "nominatedPods": "Refuse" | "Evaluate" | "EvaluateAll",   (other pods' nominations, see ksg_add_nominated_pod)
  *    "preemptNominatedPods": "Refuse" | "EvaluateAll",         (ksg_preempt under them, see ksg_add_nominated_pod)
- *    "device": 0, "distributed": {"worldSize": 1, "rank": 0, "ncclId": "<hex>"}}
+ *    "device": 0, "distributed": {"worldSize": 1, "rank": 0, "ncclId": "<hex>",
+ *                                 "diagnosis": false, "nominations": false}}    (the node-sharded section below)
  * Absent keys take the upstream defaults.  Returns NULL on failure (ksg_create_error()). */
 ksg_ctx *ksg_create(const char *config_json, size_t len);
 const char *ksg_create_error(void);
@@ -265,7 +266,9 @@ int ksg_forget(ksg_ctx *ctx, int32_t handle);
  *                       launches rather than a persistent loop.  ksg_preempt is still refused for (a)-(c),
  *                       unless "preemptNominatedPods" (below) says otherwise.
  * Any other value fails ksg_create (an invalid argument), and so do "Evaluate" and "EvaluateAll" on a node-sharded
- * context.
+ * context that was not created with "distributed": {..., "nominations": true} (the node-sharded section below).
+ * On a context with that key every rank must receive the same ksg_add_nominated_pod / ksg_delete_nominated_pod calls,
+ * in the same order relative to its scheduling calls: each rank stages its own copy of the nominee table.
  * The ksg_create key "preemptNominatedPods" selects what ksg_preempt does for a preemptor in a pair (a)-(c):
  *   "Refuse" (default)  KSG_ENOTSUP, as above.
  *   "EvaluateAll"       valid only with "nominatedPods": "EvaluateAll" (ksg_create fails otherwise, naming both
@@ -375,6 +378,22 @@ int ksg_preempt(ksg_ctx *ctx, int32_t handle, const char *args_json, size_t args
  * group none of whose ranks opted in refuses at once, without waiting for a peer).  RCCL ranks have no host channel
  * to check it through: like the rest of the config it is the caller's contract, and ranks that disagree leave the
  * opted-in ranks waiting in the collective.
+ * "nominations": true inside "distributed" (default false) opts the context into nominated pods.  Without it a
+ * node-sharded context returns KSG_ENOTSUP from ksg_pod_compile for a pod with status.nominatedNodeName and
+ * ksg_create refuses "nominatedPods": "Evaluate" / "EvaluateAll".  With it such a pod compiles and schedules -- the
+ * rank whose node range holds the nominated node evaluates it alone, one more all-reduce of two words carries the
+ * outcome, and every rank places the pod there or goes on to the full pass, the failed node counted once -- and all
+ * three "nominatedPods" values are accepted, as is "preemptNominatedPods": "EvaluateAll" together with
+ * "nominatedPods": "EvaluateAll".  Contract: every rank is created with the same value, and every rank receives the
+ * same ksg_add_nominated_pod / ksg_delete_nominated_pod calls in the same order relative to its scheduling calls.
+ * Without a transport the key is an invalid argument and ksg_create fails.  An in-process group checks the value at
+ * its first ksg_schedule_one / ksg_schedule_batch, before anything is enqueued: ranks that disagree all return
+ * KSG_EINVAL there and at every later scheduling call, and schedule nothing.  It also compares, at every launch of a
+ * persistent loop that every rank reaches, whether each rank has a nominee table staged, and returns KSG_EINVAL on
+ * every rank without launching when they differ.  That is a safety net, not a guarantee: the all-reduce path has no
+ * such check, and ranks whose tables differ may already disagree on whether a batch takes a loop at all, which ends
+ * in the rendezvous timeout (KSG_EDEVICE).  RCCL ranks have no host channel for either check: the caller's contract.  Not built
+ * on node-sharded contexts: OpportunisticBatching and the resident single-pod loops.
  * ksg_comm_unique_id writes ncclGetUniqueId as 256 hex characters + NUL (rank 0 calls it and
  * hands it to the other ranks) and returns the length. */
 int ksg_comm_unique_id(char *buf, size_t cap);
@@ -408,6 +427,13 @@ int ksg_debug_relayouts(const ksg_ctx *ctx, uint64_t *full, uint64_t *gather);
  * group then re-ran over the all-reduce path (every rank having given up at the same pod).
  * Both stay 0 in a healthy run; the tests assert it. */
 int ksg_debug_loop_stats(const ksg_ctx *ctx, uint64_t *give_ups, uint64_t *retries);
+
+/* Which k_sched_loop instance an in-process group's last loop launch dispatched (per process, recorded where the
+ * leader launches it): the runtime's name of the kernel (hipKernelNameRefByPtr: the code object's symbol, e.g.
+ * _ZN3ksg18k_sched_loop_groupILi2ELi1EEEvPKNS_12LoopGroupArgEi), NUL-terminated into buf; empty before the first such
+ * launch.  Returns its length, or KSG_EINVAL if cap is too small.  A launch with no nominee table staged runs
+ * k_sched_loop_group (or its _diag twin), one with a table k_sched_loop_group_nom. */
+int ksg_debug_group_loop_kernel(char *buf, size_t cap);
 
 /* k_sched_loop's lean selection path (config "loopLeanSelect", default true): the pods handed to
  * k_sched_loop since the context was created, while the key was on, that the path takes (*lean: compiled with raw
@@ -458,8 +484,11 @@ int ksg_debug_pod_signature(const char *config_json, size_t config_len, const ch
  * XS_CNT, XS_BELOW, XS_WORDS and kPreBits (returns 21, KSG_EINVAL if cap is smaller).  ksg_debug_pack_best is
  * the (TotalScore, heap pre-order) key every exchange B carries (selectHost, schedule_one.go:1005-1085).
  * ksg_debug_gran_a packs a persistent loop's exchange-A granule payload (which 0: {below | count}, which 1:
- * {max raw NodeAffinity + 1 | max raw TaintToleration + 1}, 0 when count is 0); _decode inverts both. */
+ * {max raw NodeAffinity + 1 | max raw TaintToleration + 1}, 0 when count is 0); _decode inverts both.
+ * ksg_debug_exchange_layout_ext fills the same 21 entries and appends what later exchanges added: [21..23] the
+ * own-nomination vector's XN_PLACED, XN_STATUS and XN_WORDS ("distributed": {"nominations": true}); returns 24. */
 int ksg_debug_exchange_layout(int32_t *out, int32_t cap);
+int ksg_debug_exchange_layout_ext(int32_t *out, int32_t cap);
 uint64_t ksg_debug_pack_best(int64_t total, uint32_t pos);
 uint64_t ksg_debug_gran_a(int32_t which, uint32_t count, uint32_t below, int64_t max_taint, int64_t max_na);
 int ksg_debug_gran_a_decode(uint64_t g0, uint64_t g1, uint32_t *count, uint32_t *below, int64_t *taint_p1,

@@ -572,6 +572,16 @@ static_assert(XA_PROC < XA_WORDS, "XA layout");
 enum XsWord : int { XS_CNT = 0, XS_BELOW = kMaxShards, XS_WORDS = 2 * kMaxShards };
 enum XpWord : int { XP_MAX_PTS = 0, XP_NMIN_PTS = 1, XP_WORDS = 4 };
 enum XbWord : int { XB_KEY = 0, XB_NODE = kMaxShards, XB_WORDS = 2 * kMaxShards };
+// The pod's own nominated node (distributed.nominations): only the rank whose block range holds the
+// node evaluates it (k_nominated_shard) and publishes; every other rank leaves zeros, the identity of the MAX.
+enum XnWord : int {
+  XN_PLACED = 0,  // 1 + (the node's filters passed: the pod is placed there)
+  XN_STATUS = 1,  // 1 + the node's packed Filter status word.  No kernel reads it back: the owner alone stores the
+                  // failed node's status (the node is in its range).  Carried so that every rank's vector shows why
+                  // the node failed (debugging) and for the protocol rehearsal over gloo.
+  XN_WORDS = 2,
+};
+static_assert(XN_PLACED == 0 && XN_STATUS == 1 && XN_WORDS == 2, "XN layout (ksg_debug_exchange_layout)");
 struct RankPtrs { unsigned long long* p[kMaxShards]; };  // every rank's exchange vector (local transport)
 // One node's static columns (NodeInfo.node) for an in-place update of the mirror, flushed in bulk
 // at the next cycle (Cluster::flush_node_updates -> k_node_update).  Variable parts live in pools

@@ -21,6 +21,8 @@
 #include <hip/hip_ext.h>
 #include <hip/hip_runtime.h>
 
+#include <atomic>
+
 #include "device.hpp"
 
 namespace ksg {
@@ -1735,11 +1737,22 @@ __device__ __forceinline__ uint32_t pod_rot_in(const BatchView& b, const PodDesc
   return d.prev_pod < 0 ? ps->rot_in : b.stats[d.prev_pod].rot_out;
 }
 
-__global__ __launch_bounds__(kBlock) void k_sample_shard_a(MirrorView m, BatchView b, ShardView sv, int pod) {
+// OWN (the five kernels below): the instances a pod with status.nominatedNodeName runs on a context with
+// distributed.nominations (the *_own kernels at the end of the file).  k_nominated_apply before them placed the pod
+// on its nominated node (every launch then returns at once, publishing an empty share; k_select_shard still clears
+// the histograms), or left nom_failed, and the failed node counts once in processedNodes (k_sample_find's rule).
+template <bool OWN>
+__device__ __forceinline__ void sample_shard_a(const MirrorView& m, const BatchView& b, const ShardView& sv, int pod) {
   const uint8_t* base = b.descs + b.desc_off[pod];
   const PodDesc& d = *reinterpret_cast<const PodDesc*>(base);
   PodStats* ps = b.stats + pod;
   unsigned long long* x = sv.xs + (size_t)pod * XS_WORDS;
+  if constexpr (OWN) {
+    if (ps->ob_done) {  // k_nominated_apply kept nextStartNodeIndex (rot_out)
+      if (threadIdx.x < XS_WORDS) x[threadIdx.x] = 0ull;
+      return;
+    }
+  }
   const uint32_t rot_in = pod_rot_in(b, d, ps);
   if (d.flags & DF_PREFILTER_REJECT) {  // the cycle ends before findNodesThatPassFilters (:635-648)
     if (threadIdx.x == 0) {
@@ -1780,14 +1793,44 @@ __global__ __launch_bounds__(kBlock) void k_sample_shard_a(MirrorView m, BatchVi
     x[w] = v;
   }
 }
+__global__ __launch_bounds__(kBlock) void k_sample_shard_a(MirrorView m, BatchView b, ShardView sv, int pod) {
+  sample_shard_a<false>(m, b, sv, pod);
+}
+
+// The nominated node that failed alone (PodStats::nom_failed) is in NodeToStatus: it counts once more in
+// processedNodes unless the full pass reached it -- rotated position < processed; outside a PreFilterResult list:
+// never (k_sample_find).  Every rank holds nom_failed, so whichever rank derives processedNodes adds it, once.
+__device__ __forceinline__ uint32_t own_failed_extra(const PodStats* ps, bool sub, const int32_t* subset, int cnt, int s,
+                                                     uint32_t rot_in, int N, uint32_t processed) {
+  if (!ps->nom_failed) return 0u;  // (uniform over the block)
+  const int nf = (int)ps->nom_failed - 1;
+  int pos = -1;
+  if (!sub) {
+    pos = (nf - s + N) % N;
+  } else {
+    __shared__ int s_nf;
+    __syncthreads();
+    if (threadIdx.x == 0) s_nf = -1;
+    __syncthreads();
+    for (int q = threadIdx.x; q < cnt; q += kBlock)
+      if (subset[q] == nf) s_nf = q;
+    __syncthreads();
+    if (s_nf >= 0) pos = (s_nf - (int)(rot_in % (uint32_t)cnt) + cnt) % cnt;
+  }
+  return (pos < 0 || pos >= (int)processed) ? 1u : 0u;
+}
 
 // cut = 0 (DF_ROTDEV without DF_SAMPLE): nothing is cut and no XS exchange ran; processedNodes is
 // the whole list.
-__global__ __launch_bounds__(kBlock) void k_sample_shard_b(MirrorView m, BatchView b, ShardView sv, int pod, int cut) {
+template <bool OWN>
+__device__ __forceinline__ void sample_shard_b(const MirrorView& m, const BatchView& b, const ShardView& sv, int pod, int cut) {
   const uint8_t* base = b.descs + b.desc_off[pod];
   const PodDesc& d = *reinterpret_cast<const PodDesc*>(base);
   PodStats* ps = b.stats + pod;
   if (d.flags & DF_PREFILTER_REJECT) return;
+  if constexpr (OWN) {
+    if (ps->ob_done) return;
+  }
   const unsigned long long* x = sv.xs + (size_t)pod * XS_WORDS;
   const bool sub = (d.flags & DF_SUBSET) != 0;
   const int32_t* subset = at<int32_t>(base, d.subset_off);
@@ -1805,9 +1848,11 @@ __global__ __launch_bounds__(kBlock) void k_sample_shard_b(MirrorView m, BatchVi
       if (r == sv.rank) c = cr;
     }
   if (!cut || F <= K) {  // every feasible node is kept
+    uint32_t extra = 0;
+    if constexpr (OWN) extra = own_failed_extra(ps, sub, subset, cnt, s, pod_rot_in(b, d, ps), N, (uint32_t)cnt);
     if (threadIdx.x == 0) {
       ps->samp_end = -1;
-      ps->processed = (uint32_t)cnt;
+      ps->processed = (uint32_t)cnt + extra;
       ps->keep[0] = 0;
       ps->keep[1] = N;
       ps->keep[2] = ps->keep[3] = 0;
@@ -1833,6 +1878,7 @@ __global__ __launch_bounds__(kBlock) void k_sample_shard_b(MirrorView m, BatchVi
     } else {
       processed = (uint32_t)((end - s + N) % N);
     }
+    if constexpr (OWN) processed += own_failed_extra(ps, sub, subset, cnt, s, pod_rot_in(b, d, ps), N, processed);
   }
   // kept global ranks: [below, min(below + K, F)) and [0, below + K - F) when it wraps
   const uint32_t lo[2] = {below, 0u};
@@ -1853,13 +1899,23 @@ __global__ __launch_bounds__(kBlock) void k_sample_shard_b(MirrorView m, BatchVi
     for (int j = 0; j < 4; ++j) ps->keep[j] = iv[j];
   }
 }
+__global__ __launch_bounds__(kBlock) void k_sample_shard_b(MirrorView m, BatchView b, ShardView sv, int pod, int cut) {
+  sample_shard_b<false>(m, b, sv, pod, cut);
+}
 
 // k_xpack_a (1 block): this rank's share of the first exchange -- feasible count, feasible nodes
 // before nextStartNodeIndex, PodTopologySpread non-ignored count, normalisation maxima/minima.
-__global__ __launch_bounds__(kBlock) void k_xpack_a(BatchView b, ShardView sv, int pod) {
+template <bool OWN>
+__device__ __forceinline__ void xpack_a(const BatchView& b, const ShardView& sv, int pod) {
   const uint8_t* base = b.descs + b.desc_off[pod];
   const PodDesc& d = *reinterpret_cast<const PodDesc*>(base);
   const PodStats* ps = b.stats + pod;
+  if constexpr (OWN) {
+    if (ps->ob_done) {  // (blk_cnt is another pod's: k_filter_score returned at once)
+      if (threadIdx.x < XA_WORDS) sv.xa[(size_t)pod * XA_WORDS + threadIdx.x] = 0ull;
+      return;
+    }
+  }
   const int k0 = sv.blk0, k1 = sv.blk0 + sv.nblk;
   __shared__ uint32_t s_red[kBlock / 64];
   uint32_t c = 0;
@@ -1889,6 +1945,7 @@ __global__ __launch_bounds__(kBlock) void k_xpack_a(BatchView b, ShardView sv, i
     x[w] = v;
   }
 }
+__global__ __launch_bounds__(kBlock) void k_xpack_a(BatchView b, ShardView sv, int pod) { xpack_a<false>(b, sv, pod); }
 
 // k_unpack_pts (1 block): after the first exchange (and the all-reduce of the ScheduleAnyway
 // domain-presence words), the global topology sizes PodTopologySpread.Score normalises with.
@@ -1933,18 +1990,28 @@ __global__ void k_xpack_p(BatchView b, ShardView sv, int pod) {
 
 // k_select_shard: k_select over this rank's blocks with the all-reduced statistics; the last
 // block writes this rank's best (key, node) into the final exchange vector.
-__global__ __launch_bounds__(kBlock) void k_select_shard(MirrorView m, BatchView b, ShardView sv, int pod) {
+template <bool OWN>
+__device__ __forceinline__ void select_shard(const MirrorView& m, const BatchView& b, const ShardView& sv, int pod) {
   const uint8_t* base = b.descs + b.desc_off[pod];
   const PodDesc& d = *reinterpret_cast<const PodDesc*>(base);
   PodStats* ps = b.stats + pod;
   const unsigned long long* xa = sv.xa + (size_t)pod * XA_WORDS;
   const unsigned long long* xp = sv.xp + (size_t)pod * XP_WORDS;
   const int blk = sv.blk0 + blockIdx.x;
+  if constexpr (OWN) {
+    if (ps->ob_done) {  // placed on its nominated node: only the histograms to clear (k_select), and an empty share
+      for (int w = blockIdx.x * kBlock + threadIdx.x; w < d.arena_words; w += gridDim.x * kBlock) b.arena[w] = 0ull;
+      if (blockIdx.x == 0 && threadIdx.x < XB_WORDS) sv.xb[(size_t)pod * XB_WORDS + threadIdx.x] = 0ull;
+      return;
+    }
+  }
   if ((d.flags & (DF_EVAL_OUT | DF_SAMPLE)) == (DF_EVAL_OUT | DF_SAMPLE) && xa[XA_END] && sv.nblk > 0) {
     // a cut feasible list: nodes past the cut were never processed (result[i] == nil,
     // schedule_one.go:845-850)
     const int i = blk * kBlock + threadIdx.x;
-    if (i < m.n && !in_cyclic(i, (int)ps->rot, (int)(xa[XA_END] - 1ull))) b.status[i] = 0u;
+    bool clear = i < m.n && !in_cyclic(i, (int)ps->rot, (int)(xa[XA_END] - 1ull));
+    if constexpr (OWN) clear = clear && ps->nom_failed != (uint32_t)i + 1u;  // (in NodeToStatus: k_sample_apply's rule)
+    if (clear) b.status[i] = 0u;
   }
   if (sv.nblk == 0) {  // an empty shard publishes an empty share and still zeroes its arena
     for (int w = threadIdx.x; w < d.arena_words; w += kBlock) b.arena[w] = 0ull;
@@ -1989,13 +2056,20 @@ __global__ __launch_bounds__(kBlock) void k_select_shard(MirrorView m, BatchView
     xb[w] = v;
   }
 }
+__global__ __launch_bounds__(kBlock) void k_select_shard(MirrorView m, BatchView b, ShardView sv, int pod) {
+  select_shard<false>(m, b, sv, pod);
+}
 
 // k_commit (1 thread): the winner over all ranks (distinct ranks hold distinct feasible
 // positions, so the packed keys never tie), result + AssumePod on this replica.
-__global__ void k_commit(MirrorView m, BatchView b, ShardView sv, int pod) {
+template <bool OWN>
+__device__ __forceinline__ void commit_shard(const MirrorView& m, const BatchView& b, const ShardView& sv, int pod) {
   const uint8_t* base = b.descs + b.desc_off[pod];
   const PodDesc& d = *reinterpret_cast<const PodDesc*>(base);
   PodStats* ps = b.stats + pod;
+  if constexpr (OWN) {
+    if (ps->ob_done) return;  // k_nominated_apply committed the pod on this replica
+  }
   const unsigned long long* xa = sv.xa + (size_t)pod * XA_WORDS;
   const unsigned long long* xb = sv.xb + (size_t)pod * XB_WORDS;
   uint32_t F = 0;
@@ -2013,6 +2087,7 @@ __global__ void k_commit(MirrorView m, BatchView b, ShardView sv, int pod) {
   }
   commit_result(m, b, base, d, ps, pod, F, node, best);
 }
+__global__ void k_commit(MirrorView m, BatchView b, ShardView sv, int pod) { commit_shard<false>(m, b, sv, pod); }
 
 // k_max_reduce: the in-process (same-device) all-reduce of the local communicator:
 // dst[w] = max over the ranks' vectors.  Safe in place: max is idempotent, so a rank reading a
@@ -3262,7 +3337,7 @@ template <int NW, int MS>
 __global__ __launch_bounds__(NW * 64 + 128) void k_sched_loop_group(const LoopGroupArg* __restrict__ ga, int G) {
   const int r = (int)blockIdx.x / G;
   const LoopGroupArg& a = ga[r];
-  // (node-sharded contexts refuse nominatedPods "Evaluate": no table)
+  // (no nominee table: a group's launch with one staged runs k_sched_loop_group_nom, at the end of this file)
   sched_loop_body<NW, false, MS, true, false>(a.m, a.b, a.lv, (int)blockIdx.x - r * G);
 }
 
@@ -5383,7 +5458,14 @@ __global__ __launch_bounds__(kBlock) void k_nom_topo(MirrorView m, BatchView b, 
 // k_sched_loop, byte for byte the same code, then took 4.23 us per pod instead of 4.18 in bench.py's default
 // workload (profiles/nominated_preempt_ab.txt).  These read-only bytes make the move a whole 64 KiB, which keeps
 // every kernel's address modulo 4, 8 and 64 KiB where it was.  Nothing reads them.
-__device__ __attribute__((used)) const unsigned char k_text_phase_pad[0xEBE0] = {};
+// The kernels for nominated pods on node-sharded contexts (the end of this file) moved things again: 0x2f00 bytes of
+// metadata in front of .text, and the plain (non-template) ones among them are emitted behind the other plain
+// kernels but in front of every template instance, 0xc200 bytes of code -- every k_sched_loop, k_agg_loop,
+// k_filter_score and k_select instance moved by 0xf100.  0xf00 more bytes here make that a whole 64 KiB as well (the
+// plain kernels in front of the new ones, none of them on the loops' path, move by 0x3e00).  Both readings at C2
+// (profiles/sharded_nominations_bench_ab.txt): k_sched_loop 3.94-3.95 us per pod with and without the 0xF00, against
+// the parent's 3.97-3.98 -- C2 did not need them; they keep every loop instance where it lay modulo 64 KiB.
+__device__ __attribute__((used)) const unsigned char k_text_phase_pad[0xEBE0 + 0xF00] = {};
 
 }  // namespace ksg
 
@@ -5409,21 +5491,22 @@ hipError_t launch_filter_score(const MirrorView& m, const BatchView& b, int pod,
   }
   return hipGetLastError();
 }
-// the two-pass instances a marked pod runs (DF_NOM_TOPO; every node block)
+// the two-pass instances a marked pod runs (DF_NOM_TOPO; blk0/nblk as launch_filter_score: a node-sharded rank's
+// own blocks, nblk < 0 every node block)
 hipError_t launch_filter_score_nt(const MirrorView& m, const BatchView& b, int pod, hipStream_t s, hipEvent_t t0,
-                                  hipEvent_t t1, bool lds) {
-  const int nblk = (m.n + kBlock - 1) / kBlock;
+                                  hipEvent_t t1, bool lds, int blk0, int nblk) {
+  if (nblk < 0) nblk = (m.n + kBlock - 1) / kBlock;
   if (nblk == 0) return hipSuccess;
   if (lds) {
     if (t0)
-      hipExtLaunchKernelGGL(k_filter_score_nt<true>, dim3(nblk), dim3(kBlock), 0, s, t0, t1, 0, m, b, pod, 0);
+      hipExtLaunchKernelGGL(k_filter_score_nt<true>, dim3(nblk), dim3(kBlock), 0, s, t0, t1, 0, m, b, pod, blk0);
     else
-      hipLaunchKernelGGL(k_filter_score_nt<true>, dim3(nblk), dim3(kBlock), 0, s, m, b, pod, 0);
+      hipLaunchKernelGGL(k_filter_score_nt<true>, dim3(nblk), dim3(kBlock), 0, s, m, b, pod, blk0);
   } else {
     if (t0)
-      hipExtLaunchKernelGGL(k_filter_score_nt<false>, dim3(nblk), dim3(kBlock), 0, s, t0, t1, 0, m, b, pod, 0);
+      hipExtLaunchKernelGGL(k_filter_score_nt<false>, dim3(nblk), dim3(kBlock), 0, s, t0, t1, 0, m, b, pod, blk0);
     else
-      hipLaunchKernelGGL(k_filter_score_nt<false>, dim3(nblk), dim3(kBlock), 0, s, m, b, pod, 0);
+      hipLaunchKernelGGL(k_filter_score_nt<false>, dim3(nblk), dim3(kBlock), 0, s, m, b, pod, blk0);
   }
   return hipGetLastError();
 }
@@ -5717,16 +5800,32 @@ static hipError_t launch_sched_loop_group_diag(const LoopGroupArg* ga, int world
                                                hipEvent_t t1, int unit);
 static hipError_t launch_agg_loop_group_diag(const AggGroupArg* ga, int world, int nwg, hipStream_t s, hipEvent_t t0,
                                              hipEvent_t t1);
+// (nom: the leader's MirrorView::nom is set -- the instances with the overlay, defined last too)
+hipError_t launch_sched_loop_group_nom(const LoopGroupArg* ga, int world, int nwg, hipStream_t s, hipEvent_t t0,
+                                       hipEvent_t t1, int unit, bool diag);
+// The k_sched_loop group kernel this process dispatched last (its host function; a diagnostic: which instance a
+// group's launch ran is otherwise visible only in a kernel trace).  last_group_loop_kernel: the runtime's name of it.
+static std::atomic<const void*> g_group_loop_fn{nullptr};
+#define KSG_GROUP_LOOP(kern, blk)                                           \
+  do {                                                                      \
+    g_group_loop_fn.store(reinterpret_cast<const void*>(&kern));            \
+    hipExtLaunchKernelGGL((kern), grid, dim3(blk), 0, s, t0, t1, 0, ga, nwg); \
+  } while (0)
+const char* last_group_loop_kernel() {
+  const void* f = g_group_loop_fn.load();
+  return f ? hipKernelNameRefByPtr(f, nullptr) : nullptr;
+}
 hipError_t launch_sched_loop_group(const LoopGroupArg* ga, int world, int nwg, hipStream_t s, hipEvent_t t0,
-                                   hipEvent_t t1, int unit, bool diag) {
+                                   hipEvent_t t1, int unit, bool diag, bool nom) {
+  if (nom) return launch_sched_loop_group_nom(ga, world, nwg, s, t0, t1, unit, diag);
   if (diag) return launch_sched_loop_group_diag(ga, world, nwg, s, t0, t1, unit);
   const dim3 grid(world * nwg);
   if (unit == 128 && world * nwg <= 64)
-    hipExtLaunchKernelGGL((k_sched_loop_group<2, 1>), grid, dim3(2 * 64 + 128), 0, s, t0, t1, 0, ga, nwg);
+    KSG_GROUP_LOOP((k_sched_loop_group<2, 1>), 2 * 64 + 128);
   else if (unit == 128)
-    hipExtLaunchKernelGGL((k_sched_loop_group<2, kMaxSweep>), grid, dim3(2 * 64 + 128), 0, s, t0, t1, 0, ga, nwg);
+    KSG_GROUP_LOOP((k_sched_loop_group<2, kMaxSweep>), 2 * 64 + 128);
   else
-    hipExtLaunchKernelGGL((k_sched_loop_group<4, kMaxSweep>), grid, dim3(kLoopThreads), 0, s, t0, t1, 0, ga, nwg);
+    KSG_GROUP_LOOP((k_sched_loop_group<4, kMaxSweep>), kLoopThreads);
   return hipGetLastError();
 }
 hipError_t launch_agg_loop_group(const AggGroupArg* ga, int world, int nwg, hipStream_t s, hipEvent_t t0, hipEvent_t t1,
@@ -5889,8 +5988,8 @@ static hipError_t launch_agg_loop_diag(const MirrorView& m, const BatchView& b, 
 static hipError_t launch_sched_loop_group_diag(const LoopGroupArg* ga, int world, int nwg, hipStream_t s, hipEvent_t t0,
                                                hipEvent_t t1, int unit) {
   const dim3 grid(world * nwg);
-  if (unit == 128) hipExtLaunchKernelGGL((k_sched_loop_group_diag<2>), grid, dim3(2 * 64 + 128), 0, s, t0, t1, 0, ga, nwg);
-  else hipExtLaunchKernelGGL((k_sched_loop_group_diag<4>), grid, dim3(kLoopThreads), 0, s, t0, t1, 0, ga, nwg);
+  if (unit == 128) KSG_GROUP_LOOP((k_sched_loop_group_diag<2>), 2 * 64 + 128);
+  else KSG_GROUP_LOOP((k_sched_loop_group_diag<4>), kLoopThreads);
   return hipGetLastError();
 }
 static hipError_t launch_agg_loop_group_diag(const AggGroupArg* ga, int world, int nwg, hipStream_t s, hipEvent_t t0,
@@ -6918,6 +7017,170 @@ hipError_t launch_sum_reduce(int32_t* dst, const RankPtrs& src, int nsrc, size_t
   hipLaunchKernelGGL(k_sum_reduce, dim3(nb < 64 ? (nb > 0 ? (unsigned)nb : 1u) : 64u), dim3(kBlock), 0, s, dst, src, nsrc,
                      count);
   return hipGetLastError();
+}
+
+// ---- nominated pods on a node-sharded context (distributed.nominations) ---------------------------
+// (every kernel below is defined behind k_sum_reduce: the kernels before them lie where they lay without them)
+//
+// The pod's own nominated node.  evaluateNominatedNode (k_nominated) needs the node's columns as the batch left
+// them, and only the rank whose block range holds the node is sure to have them: a peer's replica of that node may
+// wait for the next cycle's upload after a sharded k_agg_loop run.  So the owner alone runs the node's filters and
+// publishes the outcome (XnWord; the other ranks publish zeros), one all-reduce (MAX) carries it to every rank, and
+// k_nominated_apply does on every replica what k_nominated does on one.  The pod-table counts (ArenaTopo) are
+// replicated, so the owner's pass reads what an unsharded context's would.
+template <bool NT>
+__device__ __forceinline__ void nominated_shard(const MirrorView& m, const BatchView& b, const ShardView& sv,
+                                                unsigned long long* xn, int pod) {
+  if (threadIdx.x != 0) return;
+  const uint8_t* base = b.descs + b.desc_off[pod];
+  const PodDesc& d = *reinterpret_cast<const PodDesc*>(base);
+  PodStats* ps = b.stats + pod;
+  unsigned long long* x = xn + (size_t)pod * XN_WORDS;
+  x[XN_PLACED] = 0ull;
+  x[XN_STATUS] = 0ull;
+  if (!(d.flags & DF_NOMINATED) || (d.flags & DF_PREFILTER_REJECT)) return;
+  const int nn = d.nominated_node;
+  if (nn < 0 || nn >= m.n) return;
+  if (nn < sv.blk0 * kBlock || nn >= (sv.blk0 + sv.nblk) * kBlock) return;  // another rank's node
+  int64_t rt = 0;
+  const uint32_t st = run_filters<true, NT>(m, load_core(m, nn), base, d, nn, &rt, ArenaTopo{ps, b.arena}, 0);
+  // (the node is in this rank's range: k_eval_pack and the sharded k_diag_reduce carry its status from here)
+  if (st != 0 && (d.flags & (DF_EVAL_OUT | DF_DIAG))) b.status[nn] = st;
+  x[XN_PLACED] = st == 0 ? 2ull : 1ull;
+  x[XN_STATUS] = 1ull + (unsigned long long)st;
+}
+__global__ void k_nominated_shard(MirrorView m, BatchView b, ShardView sv, unsigned long long* xn, int pod) {
+  nominated_shard<false>(m, b, sv, xn, pod);
+}
+__global__ void k_nominated_shard_nt(MirrorView m, BatchView b, ShardView sv, unsigned long long* xn, int pod) {
+  nominated_shard<true>(m, b, sv, xn, pod);
+}
+// k_nominated_apply (one thread, every rank, behind the all-reduce of the pod's XnWord vector): placed -- the same
+// AssumePod on every replica, as k_commit's; failed -- nom_failed on every rank (the *_own kernels count it once).
+// A vector still zero (no rank owns the node: not reachable, every snapshot node is in one range) changes nothing,
+// and the full pass decides.
+__global__ void k_nominated_apply(MirrorView m, BatchView b, const unsigned long long* xn, int pod) {
+  if (threadIdx.x != 0) return;
+  const uint8_t* base = b.descs + b.desc_off[pod];
+  const PodDesc& d = *reinterpret_cast<const PodDesc*>(base);
+  PodStats* ps = b.stats + pod;
+  const unsigned long long placed = xn[(size_t)pod * XN_WORDS + XN_PLACED];
+  if (placed == 0ull) return;
+  const int nn = d.nominated_node;
+  if (placed == 1ull) {
+    ps->nom_failed = (uint32_t)nn + 1u;
+    return;
+  }
+  if (d.flags & DF_ROTDEV) {  // nextStartNodeIndex stays
+    ps->rot_out = d.prev_pod < 0 ? ps->rot_in : b.stats[d.prev_pod].rot_out;
+    ps->processed = 1;
+  }
+  commit_result(m, b, base, d, ps, pod, 1u, nn, 0ull);
+  b.results[pod].hinted = 2u;
+  b.results[pod].evaluated = 1;  // EvaluatedNodes = 1 + diagnosis.NodeToStatus.Len() (no failure yet)
+  ps->ob_done = 2u;
+}
+// the rest of such a pod's cycle (OWN, above k_sample_shard_a)
+__global__ __launch_bounds__(kBlock) void k_sample_shard_a_own(MirrorView m, BatchView b, ShardView sv, int pod) {
+  sample_shard_a<true>(m, b, sv, pod);
+}
+__global__ __launch_bounds__(kBlock) void k_sample_shard_b_own(MirrorView m, BatchView b, ShardView sv, int pod, int cut) {
+  sample_shard_b<true>(m, b, sv, pod, cut);
+}
+__global__ __launch_bounds__(kBlock) void k_xpack_a_own(BatchView b, ShardView sv, int pod) { xpack_a<true>(b, sv, pod); }
+__global__ __launch_bounds__(kBlock) void k_select_shard_own(MirrorView m, BatchView b, ShardView sv, int pod) {
+  select_shard<true>(m, b, sv, pod);
+}
+__global__ void k_commit_own(MirrorView m, BatchView b, ShardView sv, int pod) { commit_shard<true>(m, b, sv, pod); }
+
+hipError_t launch_nominated_shard(const MirrorView& m, const BatchView& b, const ShardView& sv, unsigned long long* xn,
+                                  int pod, bool nt, hipStream_t s) {
+  if (nt) hipLaunchKernelGGL(k_nominated_shard_nt, dim3(1), dim3(64), 0, s, m, b, sv, xn, pod);
+  else hipLaunchKernelGGL(k_nominated_shard, dim3(1), dim3(64), 0, s, m, b, sv, xn, pod);
+  return hipGetLastError();
+}
+hipError_t launch_nominated_apply(const MirrorView& m, const BatchView& b, const unsigned long long* xn, int pod,
+                                  hipStream_t s) {
+  hipLaunchKernelGGL(k_nominated_apply, dim3(1), dim3(64), 0, s, m, b, xn, pod);
+  return hipGetLastError();
+}
+hipError_t launch_sample_shard_a_own(const MirrorView& m, const BatchView& b, const ShardView& sv, int pod, hipStream_t s) {
+  hipLaunchKernelGGL(k_sample_shard_a_own, dim3(1), dim3(kBlock), 0, s, m, b, sv, pod);
+  return hipGetLastError();
+}
+hipError_t launch_sample_shard_b_own(const MirrorView& m, const BatchView& b, const ShardView& sv, int pod, bool cut,
+                                     hipStream_t s) {
+  hipLaunchKernelGGL(k_sample_shard_b_own, dim3(1), dim3(kBlock), 0, s, m, b, sv, pod, cut ? 1 : 0);
+  if (cut && sv.nblk > 0)  // (k_sample_apply returns at once for a pod placed on its nominated node: ob_skip)
+    hipLaunchKernelGGL(k_sample_apply, dim3(sv.nblk), dim3(kBlock), 0, s, m, b, pod, sv.blk0, 1);
+  return hipGetLastError();
+}
+hipError_t launch_xpack_a_own(const BatchView& b, const ShardView& sv, int pod, hipStream_t s) {
+  hipLaunchKernelGGL(k_xpack_a_own, dim3(1), dim3(kBlock), 0, s, b, sv, pod);
+  return hipGetLastError();
+}
+hipError_t launch_select_shard_own(const MirrorView& m, const BatchView& b, const ShardView& sv, int pod, hipStream_t s) {
+  hipLaunchKernelGGL(k_select_shard_own, dim3(sv.nblk > 0 ? sv.nblk : 1), dim3(kBlock), 0, s, m, b, sv, pod);
+  return hipGetLastError();
+}
+hipError_t launch_commit_own(const MirrorView& m, const BatchView& b, const ShardView& sv, int pod, hipStream_t s) {
+  hipLaunchKernelGGL(k_commit_own, dim3(1), dim3(1), 0, s, m, b, sv, pod);
+  return hipGetLastError();
+}
+
+// In-process groups with a nominee table staged (nominatedPods "Evaluate" / "EvaluateAll" under
+// distributed.nominations): k_sched_loop_group's body with the overlay, as k_sched_loop's NOM instances -- every
+// sweep round, and the diagnosing twins.  Kernels of their own: the group kernels above stay what they are, and a
+// launch without a table -- the common case -- runs them.  (k_agg_loop's sharded and group instances carry the
+// overlay behind the launch's MirrorView::nom already.)
+template <int NW, bool DIAG>
+__global__ __launch_bounds__(NW * 64 + 128) void k_sched_loop_group_nom(const LoopGroupArg* __restrict__ ga, int G) {
+  const int r = (int)blockIdx.x / G;
+  const LoopGroupArg& a = ga[r];
+  sched_loop_body<NW, false, kMaxSweep, true, true, false, DIAG>(a.m, a.b, a.lv, (int)blockIdx.x - r * G);
+}
+hipError_t launch_sched_loop_group_nom(const LoopGroupArg* ga, int world, int nwg, hipStream_t s, hipEvent_t t0,
+                                       hipEvent_t t1, int unit, bool diag) {
+  const dim3 grid(world * nwg);
+  if (unit == 128 && diag) KSG_GROUP_LOOP((k_sched_loop_group_nom<2, true>), 2 * 64 + 128);
+  else if (unit == 128) KSG_GROUP_LOOP((k_sched_loop_group_nom<2, false>), 2 * 64 + 128);
+  else if (diag) KSG_GROUP_LOOP((k_sched_loop_group_nom<4, true>), kLoopThreads);
+  else KSG_GROUP_LOOP((k_sched_loop_group_nom<4, false>), kLoopThreads);
+  return hipGetLastError();
+}
+// warm_kernels / loop_occupancy for the kernels above (Engine's constructor calls them behind the others)
+hipError_t warm_kernels_nom() {
+  hipFuncAttributes a;
+  const void* fs[] = {reinterpret_cast<const void*>(&k_nominated_shard),     reinterpret_cast<const void*>(&k_nominated_shard_nt),
+                      reinterpret_cast<const void*>(&k_nominated_apply),     reinterpret_cast<const void*>(&k_sample_shard_a_own),
+                      reinterpret_cast<const void*>(&k_sample_shard_b_own),  reinterpret_cast<const void*>(&k_xpack_a_own),
+                      reinterpret_cast<const void*>(&k_select_shard_own),    reinterpret_cast<const void*>(&k_commit_own),
+                      reinterpret_cast<const void*>(&k_sched_loop_group_nom<2, false>),
+                      reinterpret_cast<const void*>(&k_sched_loop_group_nom<2, true>),
+                      reinterpret_cast<const void*>(&k_sched_loop_group_nom<4, false>),
+                      reinterpret_cast<const void*>(&k_sched_loop_group_nom<4, true>)};
+  for (const void* f : fs) {
+    const hipError_t e = hipFuncGetAttributes(&a, f);
+    if (e != hipSuccess) return e;
+  }
+  return hipSuccess;
+}
+// Workgroups of k_sched_loop_group_nom one CU holds at once: [0] 128-node unit, [1] 256-node unit (each the smaller
+// of the plain and the diagnosing instance).  A group's W * G workgroups must be resident as a whole.
+hipError_t loop_occupancy_nom(int (&occ)[2]) {
+  struct K { const void* f; int threads; int k; } ks[4] = {
+      {reinterpret_cast<const void*>(&k_sched_loop_group_nom<2, false>), 2 * 64 + 128, 0},
+      {reinterpret_cast<const void*>(&k_sched_loop_group_nom<2, true>), 2 * 64 + 128, 0},
+      {reinterpret_cast<const void*>(&k_sched_loop_group_nom<4, false>), kLoopThreads, 1},
+      {reinterpret_cast<const void*>(&k_sched_loop_group_nom<4, true>), kLoopThreads, 1}};
+  occ[0] = occ[1] = 1 << 30;
+  for (const K& q : ks) {
+    int o = 0;
+    const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&o, q.f, q.threads, 0);
+    if (e != hipSuccess) return e;
+    occ[q.k] = o < occ[q.k] ? o : occ[q.k];
+  }
+  return hipSuccess;
 }
 
 }  // namespace ksg

@@ -47,6 +47,10 @@ static int with_err(ksg_ctx* ctx, int rc) {
   return rc;
 }
 
+namespace ksg {
+const char* last_group_loop_kernel();  // kernels.hip: the k_sched_loop group kernel this process dispatched last
+}
+
 static ksg_result not_scheduled() { return ksg_result{KSG_CODE_ERROR, -1, 0, 0, 0}; }
 
 extern "C" {
@@ -82,7 +86,8 @@ ksg_ctx* ksg_create(const char* config_json, size_t len) {
       return nullptr;
     }
     if (cfg.sharded()) {  // node-sharded: join the exchange group (collective across the ranks)
-      if (cfg.nominated_evaluate) {  // (every rank has the same config, so all fail here)
+      // (every rank has the same config, so all fail here; distributed.nominations opts in)
+      if (cfg.nominated_evaluate && !cfg.shard_nominations) {
         g_create_error = std::string("nominatedPods \"") + (cfg.nominated_all ? "EvaluateAll" : "Evaluate") +
                          "\" on a node-sharded context: the sharded loops do not filter with "
                          "nominated pods; use \"Refuse\" (the default)";
@@ -239,7 +244,8 @@ int ksg_pod_compile(ksg_ctx* ctx, const char* pod_json, size_t len, int32_t* han
                  "outside the device path";
       return KSG_ENOTSUP;
     }
-    if (!p.nominated_node.empty() && ctx->engine->comm) {  // evaluateNominatedNode runs on one device's mirror
+    // evaluateNominatedNode runs on one device's mirror: the owner rank's, where distributed.nominations opted in
+    if (!p.nominated_node.empty() && ctx->engine->comm && !ctx->cluster->cfg.shard_nominations) {
       ctx->err = "pod " + p.ns + "/" + p.name + ": status.nominatedNodeName on a node-sharded context (the nominated "
                  "node's single-node pass is not sharded)";
       return KSG_ENOTSUP;
@@ -293,11 +299,39 @@ static int diag_refused(ksg_ctx* ctx) {
   return KSG_OK;
 }
 
+// distributed.nominations must be the same on every rank too (the ranks would issue different exchange sequences for
+// a pod with status.nominatedNodeName, and stage different nominee tables).  An in-process group checks it once, at
+// the first scheduling call, before anything is enqueued, as diag_refused does: only where some member opted in, so
+// a group none of whose members did never waits for a peer here.  Ranks that disagree all return KSG_EINVAL, at this
+// call and at every later one.  RCCL ranks have no host channel: the caller's contract.
+static int nom_disagreed(ksg_ctx* ctx) {
+  Engine& e = *ctx->engine;
+  if (!e.comm || !e.comm->in_process() || e.nom_agreed_) return KSG_OK;
+  const bool mine = ctx->cluster->cfg.shard_nominations;
+  if (!mine && !e.comm->nominations_opted_in()) return KSG_OK;
+  std::vector<int64_t> all;
+  if (e.comm->agree(mine ? 1 : 0, &all) != KSG_OK) {
+    ctx->err = e.comm->err;
+    return KSG_EDEVICE;
+  }
+  bool same = true;
+  for (int64_t v : all) same = same && v == all[0];
+  if (!same) {
+    std::string o;
+    for (size_t r = 0; r < all.size(); ++r) o += (r ? ", rank " : "rank ") + std::to_string(r) + ": " + (all[r] ? "true" : "false");
+    ctx->err = "distributed.nominations differs between the ranks of the group (" + o + "): nothing was scheduled";
+    return KSG_EINVAL;
+  }
+  e.nom_agreed_ = true;
+  return KSG_OK;
+}
+
 // ksg_schedule_one (diag == NULL) / ksg_schedule_one_diag.  A diagnosed cycle takes the launch path: its status
 // words are stored and k_diag_reduce follows its k_select.
 static int schedule_one(ksg_ctx* ctx, int32_t handle, uint32_t flags, ksg_result* result, ksg_eval_out* eval,
                         ksg_diagnosis* diag) {
   GUARD({
+    if (const int ra = nom_disagreed(ctx)) return ra;
     auto it = ctx->engine->queue.find(handle);
     if (it == ctx->engine->queue.end()) return KSG_ENOTFOUND;
     if (const int rn = ctx->engine->check_nominations({&it->second})) return with_err(ctx, rn);
@@ -332,6 +366,7 @@ int ksg_schedule_one_diag(ksg_ctx* ctx, int32_t handle, uint32_t flags, ksg_resu
 static int schedule_batch(ksg_ctx* ctx, const int32_t* handles, int32_t n, uint32_t flags, ksg_result* results,
                           ksg_diagnosis* diags) {
   GUARD({
+    if (const int ra = nom_disagreed(ctx)) return ra;
     if (const int rs = quiesce(ctx)) return rs;
     ctx->engine->api_t0_ = std::chrono::steady_clock::now();  // loopStamps: the handle lookups' share
     std::vector<const PodSpec*> pods;
@@ -347,10 +382,20 @@ static int schedule_batch(ksg_ctx* ctx, const int32_t* handles, int32_t n, uint3
     // nominatedPods "Evaluate": pod i sees the nominator as pods 0..i-1 left it, and an assume ends the assumed
     // pod's own nomination.  The nominee table is staged per run, so a run ends after every pod the nominator
     // holds; the pods between them -- nearly always the whole batch -- run as one.
-    if (ctx->engine->nom_evaluate() && assume && !ctx->engine->nominated.empty()) {
+    // A node-sharded context with distributed.nominations: a pod with status.nominatedNodeName is a run of its own
+    // whatever nominatedPods is.  Its run has nextStartNodeIndex on the device (Engine::rotdev), which keeps every
+    // pod of the run out of the sharded loops; alone, it leaves the plain pods around it to them.
+    const bool own_runs = ctx->engine->comm && ctx->cluster->cfg.shard_nominations;
+    bool own_any = false;
+    for (int32_t i = 0; i < n && own_runs && !own_any; ++i) own_any = !pods[(size_t)i]->nominated_node.empty();
+    const bool owner_runs = ctx->engine->nom_evaluate() && assume && !ctx->engine->nominated.empty();
+    if (owner_runs || own_any) {
       int32_t a = 0;
       for (int32_t i = 0; i < n; ++i) {
-        if (i + 1 < n && !ctx->engine->nom_owner(*pods[(size_t)i])) continue;
+        const bool ends = (owner_runs && ctx->engine->nom_owner(*pods[(size_t)i])) ||
+                          (own_any && (!pods[(size_t)i]->nominated_node.empty() ||
+                                       (i + 1 < n && !pods[(size_t)i + 1]->nominated_node.empty())));
+        if (i + 1 < n && !ends) continue;
         const std::vector<const PodSpec*> sub(pods.begin() + a, pods.begin() + i + 1);
         const std::vector<int32_t> sh(hs.begin() + a, hs.begin() + i + 1);
         const int rc = ctx->engine->run_batch_api(sub, sh, assume, results + a, nullptr, diags ? diags + a : nullptr);
@@ -630,6 +675,28 @@ int ksg_debug_exchange_layout(int32_t* out, int32_t cap) {
   if (!out || cap < n) return KSG_EINVAL;
   for (int32_t k = 0; k < n; ++k) out[k] = v[k];
   return n;
+}
+
+// ksg_debug_exchange_layout's vector with the later exchange vectors appended (its 21 entries keep their places and
+// its own length stays what its callers check): [21..23] the own-nomination vector (XnWord)
+int ksg_debug_exchange_layout_ext(int32_t* out, int32_t cap) {
+  using namespace ksg;
+  const int32_t base = ksg_debug_exchange_layout(out, cap);
+  if (base < 0) return base;
+  const int32_t v[] = {XN_PLACED, XN_STATUS, XN_WORDS};
+  const int32_t n = (int32_t)(sizeof v / sizeof v[0]);
+  if (cap < base + n) return KSG_EINVAL;
+  for (int32_t k = 0; k < n; ++k) out[base + k] = v[k];
+  return base + n;
+}
+
+int ksg_debug_group_loop_kernel(char* buf, size_t cap) {
+  const char* nm = ksg::last_group_loop_kernel();
+  if (!nm) nm = "";
+  const size_t n = std::strlen(nm);
+  if (!buf || cap < n + 1) return KSG_EINVAL;
+  std::memcpy(buf, nm, n + 1);
+  return (int)n;
 }
 
 uint64_t ksg_debug_pack_best(int64_t total, uint32_t pos) { return ksg::pack_best(total, pos); }

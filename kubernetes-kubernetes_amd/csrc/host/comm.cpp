@@ -133,6 +133,7 @@ struct LocalGroup {
   std::condition_variable cv;
   int world = 0, arrived = 0, members = 0;
   bool diagnosis = false;  // a member was created with distributed.diagnosis true (g_groups_mu)
+  bool nominations = false;  // ... with distributed.nominations true (g_groups_mu)
   uint64_t gen = 0;
   hipEvent_t launched = nullptr;  // group_launch: the leader's event after the group's dispatch
   int launch_rc = 0;              // ... and the leader's status
@@ -255,6 +256,11 @@ class LocalComm : public Comm {
     return g && g->diagnosis;
   }
 
+  bool nominations_opted_in() const override {
+    std::lock_guard<std::mutex> lk(g_groups_mu);
+    return g && g->nominations;
+  }
+
   int share_buffers(void* mine, std::vector<void*>* all) override {  // one process: the pointers themselves
     int sl = 0;
     if (!rendezvous((unsigned long long*)mine, nullptr, 0, &sl)) {
@@ -305,6 +311,12 @@ class LocalComm : public Comm {
       std::lock_guard<std::mutex> lk(g->mu);
       rc = g->launch_rc;
       done = g->launched;
+    }
+    if (rc == KSG_EINVAL) {  // the leader's check of the ranks' requests (Engine::group_launch): nothing was launched
+      err = "group launch: a nominee table is staged on some ranks of the group and not on others (every rank must "
+            "receive the same ksg_add_nominated_pod / ksg_delete_nominated_pod calls, distributed.nominations): "
+            "nothing was launched";
+      return KSG_EINVAL;
     }
     if (rc != KSG_OK) {
       err = "group launch: the leader could not enqueue the group's dispatch";
@@ -397,6 +409,7 @@ std::unique_ptr<Comm> make_comm(const Config& cfg, std::string* err) {
     }
     ++g->members;
     g->diagnosis = g->diagnosis || cfg.shard_diagnosis;
+    g->nominations = g->nominations || cfg.shard_nominations;
     c->g = g;
   }
   return c;

@@ -37,6 +37,8 @@ class Comm {
   // in-process groups: some member of the group was created with distributed.diagnosis true (RCCL ranks have no
   // host channel: false)
   virtual bool diagnosis_opted_in() const { return false; }
+  // ... with distributed.nominations true
+  virtual bool nominations_opted_in() const { return false; }
   // brackets several all-reduces that may be fused (ncclGroupStart/End)
   virtual int group_begin() { return 0; }
   virtual int group_end() { return 0; }
@@ -54,6 +56,8 @@ class Comm {
   // launch request (`req`, valid until the call returns); the leader (rank 0) makes its stream wait for every
   // rank's stream, calls leader(its stream, every rank's req) to enqueue the group's dispatch, and every other
   // rank's stream then waits for that.  RCCL ranks (a device each) launch their own loops and never call this.
+  // A leader that returns KSG_EINVAL found the ranks' requests inconsistent and launched nothing: every rank
+  // returns KSG_EINVAL.
   using GroupLaunchFn = std::function<int(hipStream_t, const std::vector<void*>&)>;
   virtual int group_launch(void* req, hipStream_t s, const GroupLaunchFn& leader) {
     err = "group_launch: only in-process groups launch their loops together";

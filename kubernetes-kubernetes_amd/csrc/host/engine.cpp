@@ -72,7 +72,7 @@ hipError_t launch_agg_loop(const MirrorView& m, const BatchView& b, const AggVie
 hipError_t launch_put_group_arg(const LoopGroupArg& a, LoopGroupArg* dst, hipStream_t s);
 hipError_t launch_put_group_arg(const AggGroupArg& a, AggGroupArg* dst, hipStream_t s);
 hipError_t launch_sched_loop_group(const LoopGroupArg* ga, int world, int nwg, hipStream_t s, hipEvent_t t0,
-                                   hipEvent_t t1, int unit, bool diag);
+                                   hipEvent_t t1, int unit, bool diag, bool nom);
 hipError_t launch_agg_loop_group(const AggGroupArg* ga, int world, int nwg, hipStream_t s, hipEvent_t t0, hipEvent_t t1,
                                  bool diag);
 hipError_t warm_kernels();
@@ -84,7 +84,23 @@ hipError_t launch_ob_store(const BatchView& b, int pod, hipStream_t s);
 // the two-pass instances of the node pass, k_nominated and k_ob_hint
 hipError_t launch_nom_topo(const MirrorView& m, const BatchView& b, int pod, const PodDesc& d, int nrec, hipStream_t s);
 hipError_t launch_filter_score_nt(const MirrorView& m, const BatchView& b, int pod, hipStream_t s, hipEvent_t t0,
-                                  hipEvent_t t1, bool lds);
+                                  hipEvent_t t1, bool lds, int blk0 = 0, int nblk = -1);
+// distributed.nominations: the pod's own nominated node on a node-sharded context -- the owner rank's
+// single-node pass, its outcome applied on every replica behind one all-reduce, and the rest of the cycle's sharded
+// kernels in the instances that skip a placed pod and count a failed node once; the in-process groups' k_sched_loop
+// with the nominee overlay
+hipError_t launch_nominated_shard(const MirrorView& m, const BatchView& b, const ShardView& sv, unsigned long long* xn,
+                                  int pod, bool nt, hipStream_t s);
+hipError_t launch_nominated_apply(const MirrorView& m, const BatchView& b, const unsigned long long* xn, int pod,
+                                  hipStream_t s);
+hipError_t launch_sample_shard_a_own(const MirrorView& m, const BatchView& b, const ShardView& sv, int pod, hipStream_t s);
+hipError_t launch_sample_shard_b_own(const MirrorView& m, const BatchView& b, const ShardView& sv, int pod, bool cut,
+                                     hipStream_t s);
+hipError_t launch_xpack_a_own(const BatchView& b, const ShardView& sv, int pod, hipStream_t s);
+hipError_t launch_select_shard_own(const MirrorView& m, const BatchView& b, const ShardView& sv, int pod, hipStream_t s);
+hipError_t launch_commit_own(const MirrorView& m, const BatchView& b, const ShardView& sv, int pod, hipStream_t s);
+hipError_t warm_kernels_nom();
+hipError_t loop_occupancy_nom(int (&occ)[2]);
 hipError_t launch_ob_hint_nt(const MirrorView& m, const BatchView& b, int pod, hipStream_t s);
 hipError_t launch_nominated_nt(const MirrorView& m, const BatchView& b, int pod, hipStream_t s);
 hipError_t launch_diag_reduce(const MirrorView& m, const BatchView& b, int pod, int32_t* rows, hipStream_t s, int blk0 = 0,
@@ -1031,9 +1047,9 @@ Engine::Engine(Cluster* cl) : c(cl) {
   if (hipDeviceGetAttribute(&cu_count, hipDeviceAttributeMultiprocessorCount, c->cfg.device) != hipSuccess)
     cu_count = 0;
   // every kernel's code object loaded before the first batch (see warm_kernels)
-  if (c->err.empty() && (warm_kernels() != hipSuccess || warm_aggregate() != hipSuccess))
+  if (c->err.empty() && (warm_kernels() != hipSuccess || warm_aggregate() != hipSuccess || warm_kernels_nom() != hipSuccess))
     c->err = "cannot load the kernels' code object on HIP device " + std::to_string(c->cfg.device);
-  if (c->err.empty() && loop_occupancy(loop_occ) != hipSuccess)
+  if (c->err.empty() && (loop_occupancy(loop_occ) != hipSuccess || loop_occupancy_nom(loop_occ_nom) != hipSuccess))
     c->err = "cannot query the persistent loops' occupancy on HIP device " + std::to_string(c->cfg.device);
 }
 
@@ -1277,7 +1293,7 @@ Engine::~Engine() {
   for (DevBuf* b : {&d_descs, &d_meta, &d_status, &d_fmask, &d_blk, &d_fixed, &d_raw, &d_out,
                     &d_total, &d_arena, &d_xa, &d_xp, &d_xb, &d_xs, &d_gran, &d_fail, &d_grp, &d_agran, &d_region, &d_astamps, &d_aspill, &d_relay,
                     &d_evg, &d_aggpeers, &d_pre, &d_seg, &d_segcnt, &d_psout, &d_pdb, &d_pick, &d_contrib_buf, &d_wide, &d_vsc,
-                    &d_ob, &d_ob_heap, &d_ob_map, &d_tcache, &d_tcw, &d_nom, &d_diag, &d_diag_sum})
+                    &d_ob, &d_ob_heap, &d_ob_map, &d_tcache, &d_tcw, &d_nom, &d_diag, &d_diag_sum, &d_xn})
     if (b->p) (void)hipFree(b->p);
   if (h_pinned) (void)hipHostFree(h_pinned);
   if (h_tcw) (void)hipHostFree(h_tcw);
@@ -1328,6 +1344,7 @@ int Engine::ensure_scratch(size_t desc_bytes, int pods, bool eval, int32_t arena
     if ((rc = ensure(d_xp, (size_t)pods * XP_WORDS * 8))) return rc;
     if ((rc = ensure(d_xb, (size_t)pods * XB_WORDS * 8))) return rc;
     if ((rc = ensure(d_xs, (size_t)pods * XS_WORDS * 8))) return rc;
+    if (c->cfg.shard_nominations && (rc = ensure(d_xn, (size_t)pods * XN_WORDS * 8))) return rc;
     HIPCHK(hipMemsetAsync(d_xp.p, 0, (size_t)pods * XP_WORDS * 8, c->stream));
   }
   if (d_arena.bytes < (size_t)arena_words * 8 + 8) {
@@ -1649,6 +1666,11 @@ int Engine::group_launch(GroupReq* req, bool agg, int nwg, int unit) {
   auto leader = [&](hipStream_t ls, const std::vector<void*>& reqs) -> int {
     if (!grp || (int)reqs.size() != W) return KSG_EDEVICE;
     auto rq = [&](int r) -> const GroupReq& { return *static_cast<const GroupReq*>(reqs[(size_t)r]); };
+    // every rank of the dispatch runs the leader's instance: a nominee table staged on some ranks only would give
+    // silently different evaluations, so nothing is launched (KSG_EINVAL on every rank, Comm::group_launch)
+    auto staged = [&](int r) { return (agg ? rq(r).aa.m.nom : rq(r).la.m.nom) != nullptr; };
+    for (int r = 1; r < W; ++r)
+      if (staged(r) != staged(0)) return KSG_EINVAL;
     for (int r = 0; r < W; ++r)
       if ((agg ? launch_put_group_arg(rq(r).aa, (AggGroupArg*)grp + r, ls)
                : launch_put_group_arg(rq(r).la, (LoopGroupArg*)grp + r, ls)) != hipSuccess)
@@ -1659,15 +1681,15 @@ int Engine::group_launch(GroupReq* req, bool agg, int nwg, int unit) {
     const hipError_t e =
         agg ? launch_agg_loop_group((const AggGroupArg*)grp, W, nwg, ls, rq(0).t0, rq(0).t1, rq(0).aa.av.diag != nullptr)
             : launch_sched_loop_group((const LoopGroupArg*)grp, W, nwg, ls, rq(0).t0, rq(0).t1, unit,
-                                      rq(0).la.lv.diag != nullptr);
+                                      rq(0).la.lv.diag != nullptr, staged(0));
     if (e != hipSuccess) return KSG_EDEVICE;
     for (int r = 1; r < W; ++r)
       if (rq(r).t1 && hipEventRecord(rq(r).t1, ls) != hipSuccess) return KSG_EDEVICE;
     return KSG_OK;
   };
-  if (comm->group_launch(req, c->stream, leader) != KSG_OK) {
+  if (const int rc = comm->group_launch(req, c->stream, leader)) {
     c->err = comm->err;
-    return KSG_EDEVICE;
+    return rc == KSG_EINVAL ? KSG_EINVAL : KSG_EDEVICE;
   }
   return KSG_OK;
 }
@@ -2281,6 +2303,9 @@ int Engine::run_batch(const std::vector<const PodSpec*>& pods, const std::vector
   const bool use_loop = loop_worth && (!comm || dx) && !eval && c->cfg.persistent_loop && NB > 0 && GS >= 1 &&
                         (int64_t)GS * kLoopMaxBlk * unit >= (int64_t)NBs * kBlock &&
                         (int64_t)GS * dev_ranks <= (int64_t)cus * loop_occ[unit == 128 ? 0 : 1] &&
+                        // (an in-process group with a nominee table staged launches k_sched_loop_group_nom)
+                        (!(comm && !rccl && m.nom != nullptr) ||
+                         (int64_t)GS * dev_ranks <= (int64_t)cus * loop_occ_nom[unit == 128 ? 0 : 1]) &&
                         (int64_t)c->taint_max_per_node < ((int64_t)1 << 24) - 1;
   // k_agg_loop: the same geometry (node-sharded: over the device exchange, world * G participants);
   // every workgroup's LDS lists must hold its nodes' pods and terms plus everything this batch can add
@@ -3218,21 +3243,40 @@ int Engine::run_sharded(const std::vector<CompiledPod>& cp, const BatchView& bv,
     if (cp[i].error) continue;
     const PodDesc& hd = *reinterpret_cast<const PodDesc*>(cp[i].blob.data());
     if (hd.flags & DF_AGGREGATE) HIPCHK(launch_aggregate(m, bv, i, hd, s));  // replicated pod table
-    if (stride > 0 && i % stride == 0 && sv.nblk > 0) {
-      HIPCHK(launch_filter_score(m, bv, i, s, tev[2 * (size_t)timed], tev[2 * (size_t)timed + 1], sv.blk0, sv.nblk,
-                                 cp[i].blob.size() <= (size_t)kBlobLds));
-      timed++;
-    } else {
-      HIPCHK(launch_filter_score(m, bv, i, s, nullptr, nullptr, sv.blk0, sv.nblk, cp[i].blob.size() <= (size_t)kBlobLds));
-    }
     int rc = KSG_OK;
+    // a marked pod with a nominee table staged (nominatedPods "EvaluateAll"): the nominees' deltas, replicated as the
+    // counts they add to, then the two-pass instances (run_batch's unsharded per-pod path)
+    const bool nt = (hd.flags & DF_NOM_TOPO) && m.nom != nullptr;
+    if (nt) HIPCHK(launch_nom_topo(m, bv, i, hd, nom_nrec_, s));
+    // The pod's own nominated node (distributed.nominations; a context without it compiles no such pod): the owner
+    // rank's single-node pass, one all-reduce, the outcome on every replica.  Every rank decides from the same
+    // PodDesc whether the exchange is issued, and the rest of the cycle is enqueued either way: a pod placed here is
+    // known on the device only, and the *_own instances return at once for it.
+    const bool own = (hd.flags & DF_NOMINATED) && !(hd.flags & DF_PREFILTER_REJECT) && hd.nominated_node >= 0 &&
+                     hd.nominated_node < m.n;
+    if (own) {
+      unsigned long long* xn = (unsigned long long*)d_xn.p;
+      if (!xn) {
+        c->err = "a pod with status.nominatedNodeName on a node-sharded context without distributed.nominations";
+        return KSG_ENOTSUP;
+      }
+      HIPCHK(launch_nominated_shard(m, bv, sv, xn, i, nt, s));
+      if ((rc = xchg(xn + (size_t)i * XN_WORDS, XN_WORDS))) return rc;
+      HIPCHK(launch_nominated_apply(m, bv, xn, i, s));
+    }
+    const bool lds = cp[i].blob.size() <= (size_t)kBlobLds;
+    const bool t = stride > 0 && i % stride == 0 && sv.nblk > 0;
+    hipEvent_t te0 = t ? tev[2 * (size_t)timed] : nullptr, te1 = t ? tev[2 * (size_t)timed + 1] : nullptr;
+    if (nt) HIPCHK(launch_filter_score_nt(m, bv, i, s, te0, te1, lds, sv.blk0, sv.nblk));
+    else HIPCHK(launch_filter_score(m, bv, i, s, te0, te1, sv.blk0, sv.nblk, lds));
+    if (t) timed++;
     if (hd.flags & DF_ROTDEV) {  // percentageOfNodesToScore: the cut needs every rank's counts first
       const bool cut = (hd.flags & DF_SAMPLE) != 0;
-      HIPCHK(launch_sample_shard_a(m, bv, sv, i, s));
+      HIPCHK(own ? launch_sample_shard_a_own(m, bv, sv, i, s) : launch_sample_shard_a(m, bv, sv, i, s));
       if (cut && (rc = xchg(sv.xs + (size_t)i * XS_WORDS, XS_WORDS))) return rc;
-      HIPCHK(launch_sample_shard_b(m, bv, sv, i, cut, s));
+      HIPCHK(own ? launch_sample_shard_b_own(m, bv, sv, i, cut, s) : launch_sample_shard_b(m, bv, sv, i, cut, s));
     }
-    HIPCHK(launch_xpack_a(bv, sv, i, s));
+    HIPCHK(own ? launch_xpack_a_own(bv, sv, i, s) : launch_xpack_a(bv, sv, i, s));
     const bool pts = (hd.score_mask & (1u << P_PTS)) != 0;
     if (comm->group_begin()) return KSG_EDEVICE;
     rc = xchg(sv.xa + (size_t)i * XA_WORDS, XA_WORDS);
@@ -3248,9 +3292,9 @@ int Engine::run_sharded(const std::vector<CompiledPod>& cp, const BatchView& bv,
       HIPCHK(launch_xpack_p(bv, sv, i, s));
       if ((rc = xchg(sv.xp + (size_t)i * XP_WORDS, XP_WORDS))) return rc;
     }
-    HIPCHK(launch_select_shard(m, bv, sv, i, s));
+    HIPCHK(own ? launch_select_shard_own(m, bv, sv, i, s) : launch_select_shard(m, bv, sv, i, s));
     if ((rc = xchg(sv.xb + (size_t)i * XB_WORDS, XB_WORDS))) return rc;
-    HIPCHK(launch_commit(m, bv, sv, i, s));
+    HIPCHK(own ? launch_commit_own(m, bv, sv, i, s) : launch_commit(m, bv, sv, i, s));
     // a diagnosed call: this rank's share of the pod's row, over its own blocks (none for an empty shard); k_commit
     // left the global outcome in the pod's result, so every rank reduces or none does
     if (hd.flags & DF_DIAG) HIPCHK(launch_diag_reduce(m, bv, i, (int32_t*)d_diag.p, s, sv.blk0, sv.nblk));

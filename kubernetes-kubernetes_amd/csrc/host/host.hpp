@@ -257,6 +257,10 @@ struct Config {
   // distributed.diagnosis: ksg_schedule_*_diag are collective calls on this sharded context;
   // off (the default): they are refused
   bool shard_diagnosis = false;
+  // distributed.nominations: this sharded context schedules pods with status.nominatedNodeName (the owner rank's
+  // single-node pass, Engine::run_sharded) and accepts nominatedPods "Evaluate" / "EvaluateAll" (DESIGN.md §6);
+  // off (the default): both are refused
+  bool shard_nominations = false;
   // a transport was configured: run the node-sharded pipeline even at worldSize 1 (tests it alone)
   bool sharded() const { return world > 1 || !nccl_id.empty() || !local_group.empty(); }
   Config();
@@ -610,7 +614,8 @@ class Engine {
   int run_batch_api(const std::vector<const PodSpec*>& pods, const std::vector<int32_t>& handles, bool assume,
                     ksg_result* results, ksg_eval_out* eval, ksg_diagnosis* diag = nullptr);
   bool diag_agreed_ = false;    // in-process group: every rank has distributed.diagnosis (checked at the first diagnosed call)
-  int fault_first_ = -1;      // the first pod loop_fault left unscheduled (-1: none), for run_batch_api
+  bool nom_agreed_ = false;     // ... every rank has the same distributed.nominations (checked at the first scheduling call)
+  int fault_first_ = -1;     // the first pod loop_fault left unscheduled (-1: none), for run_batch_api
   bool force_allreduce_ = false;  // run_batch_api's retry: no device exchange
   uint64_t loop_retries_ = 0;   // batches run_batch_api re-ran over the all-reduce path
   uint64_t loop_give_ups_ = 0;  // batches whose persistent loop gave up (forced ones included)
@@ -642,6 +647,9 @@ class Engine {
   // unit, [1] 256-node unit, [2] k_agg_loop, [3] node-sharded k_agg_loop); a loop's whole grid -- all
   // ranks' grids for in-process groups, which share the device -- must fit in cu_count * that
   int loop_occ[4] = {0, 0, 0, 0};
+  // ... of the in-process groups' k_sched_loop with the nominee overlay (loop_occupancy_nom: by unit), which a
+  // group launches when a nominee table is staged
+  int loop_occ_nom[2] = {0, 0};
   bool loop_ok(const CompiledPod& p) const;
   bool loop_bounds_ok(const CompiledPod& p) const;  // the loops' granule payload bounds
   bool agg_loop_ok(const CompiledPod& p) const;
@@ -686,6 +694,7 @@ class Engine {
   size_t h_diag_rows = 0;
   DevBuf d_arena;  // PTS/IPA histograms; kept all-zero between pods (k_select re-zeroes what it used)
   DevBuf d_xa, d_xp, d_xb, d_xs;  // node-sharded exchange vectors, one set per pod of the batch
+  DevBuf d_xn;                    // ... the own-nomination vector (XnWord; distributed.nominations)
   DevBuf d_evg;             // node-sharded evaluation output, gathered over the ranks
   DevBuf d_gran, d_fail, d_stamps;  // k_sched_loop: exchange granules (local), give-up flag, stamps
   uint64_t assume_seq_ = 0;  // assumed pods' cache uids: "<uid>#a<n>", n counted per context

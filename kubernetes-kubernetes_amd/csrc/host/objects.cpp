@@ -948,6 +948,12 @@ bool decode_config(const char* p, size_t n, Config* c, std::string* err) {
                "context diagnoses without it";
         return false;
       }
+      if (const JVal* nm = d.get(*ds, "nominations")) c->shard_nominations = nm->type == JVal::BOOL && nm->b;
+      if (c->shard_nominations && !c->sharded()) {
+        *err = "distributed.nominations: true needs a node-sharded context (ncclId or localGroup); an unsharded "
+               "context schedules nominated pods without it";
+        return false;
+      }
     }
     bool ok = true;
     d.each(d.get(r, "scoreWeights"), [&](const JVal& v) {

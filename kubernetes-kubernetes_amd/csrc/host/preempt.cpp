@@ -34,7 +34,7 @@ hipError_t launch_preempt_seg(const MirrorView& m, const BatchView& b, int pod, 
                               hipStream_t s);
 hipError_t launch_nom_topo(const MirrorView& m, const BatchView& b, int pod, const PodDesc& d, int nrec, hipStream_t s);
 hipError_t launch_filter_score_nt(const MirrorView& m, const BatchView& b, int pod, hipStream_t s, hipEvent_t t0,
-                                  hipEvent_t t1, bool lds);
+                                  hipEvent_t t1, bool lds, int blk0 = 0, int nblk = -1);
 hipError_t launch_pts_minima(const BatchView& b, int pod, int ncons, long long* mm, hipStream_t s);
 hipError_t launch_aff_totals(const BatchView& b, int pod, int nterms, long long* out, hipStream_t s);
 hipError_t launch_preempt_terms(const MirrorView& m, const BatchView& b, int pod, int32_t* contrib, hipStream_t s);

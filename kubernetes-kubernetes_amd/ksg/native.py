@@ -165,6 +165,22 @@ class Scheduler(Backend):
         return a.value, n.value
 
 
+def group_loop_kernel():
+    """The k_sched_loop instance an in-process group's last loop launch dispatched in this process, as the runtime
+    names it (ksg_debug_group_loop_kernel; "" before the first such launch, None with a library built before it)."""
+    lib = load()
+    if not hasattr(lib, "ksg_debug_group_loop_kernel"):
+        return None
+    fn = lib.ksg_debug_group_loop_kernel
+    fn.restype = C.c_int
+    fn.argtypes = [C.c_char_p, C.c_size_t]
+    buf = C.create_string_buffer(512)
+    rc = fn(buf, 512)
+    if rc < 0:
+        raise KsgError(f"ksg_debug_group_loop_kernel: rc={rc}")
+    return buf.value.decode()
+
+
 def comm_unique_id():
     """ncclGetUniqueId as hex (rank 0 creates it; every rank passes it as distributed.ncclId)."""
     lib = load()
