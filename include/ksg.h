@@ -441,6 +441,16 @@ int ksg_debug_group_loop_kernel(char *buf, size_t cap);
  * the host; both stay 0 with the key off. */
 int ksg_debug_lean_pods(const ksg_ctx *ctx, uint64_t *lean, uint64_t *general);
 
+/* Sampled pods in k_agg_loop (config "aggLoopSampled", default true; DESIGN.md §4.5 "Inside k_agg_loop").  In a
+ * context whose nextStartNodeIndex lives on the device -- percentageOfNodesToScore other than 100 (0, upstream's
+ * adaptive default, included), a profile without score plugins, OpportunisticBatching acting, or a batch holding a pod
+ * with status.nominatedNodeName -- a batch's runs of PodTopologySpread / InterPodAffinity pods go through k_agg_loop's
+ * sampling instances: the loop cuts the feasible list to numFeasibleNodesToFind and carries the rotation itself.
+ * Unsharded batch calls only, without a PreFilterResult subset and undiagnosed; node-sharded contexts, the resident
+ * one-pod calls and ksg_schedule_*_diag keep the per-pod launches for such pods.  false: every sampled
+ * PodTopologySpread / InterPodAffinity pod takes the per-pod launches, as before the key existed.  The results are
+ * the same either way; ksg_last_batch_kernel_stats names the kernel a batch's pods mostly ran in. */
+
 /* Parity diagnostic (no device needed): fills out[k] = math.Log(float64(k)) for 0 <= k < n with
  * the table PodTopologySpread's score kernel reads (topologyNormalizingWeight, podtopologyspread/
  * scoring.go:287-299: log(size + 2)).  Returns n. */

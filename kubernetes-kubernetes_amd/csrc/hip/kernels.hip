@@ -3548,10 +3548,18 @@ __device__ __forceinline__ void apply_entry(const MirrorView& m, const uint8_t* 
 // cycle ends without a feasible node wave 0 of every workgroup adds its nodes' statuses to the pod's row.
 // (SHARD / GRP: F is the count over all world * G participants, so every rank's workgroups take the branch; s_st
 // holds this workgroup's slots only -- 0 where it has no node -- and the row is this rank's own, summed on the host.)
+// SAMP: a run of sampled pods (DF_ROTDEV: percentageOfNodesToScore < 100, a no-score profile, ...),
+// unsharded batch runs only.  nextStartNodeIndex lives in LDS (s_rot[q & 1] is pod q's; nothing is evaluated ahead
+// of a placement here, so phase 1 of pod q already counts against it); after exchange A every workgroup knows F and
+// the count before the start, and with F > K the feasible list is cut to the first K of the rotated order: one more
+// exchange (M, the granule row at q + kLoopMaxPods, exchange A's slot meanings) carries the kept nodes' maxima /
+// minima, PodTopologySpread presence bits and non-ignored count, and the (K+1)-th node's processedNodes + 1 from the
+// workgroup that holds it; phase 2 keeps the rotated positions < K.  The other instances compile none of it.
 // (the body of k_agg_loop and k_agg_loop_group: w = the workgroup this block plays in its rank)
-template <bool SHARD, bool PTSS, bool RING, int MS, bool GRP, bool DIAG = false>
+template <bool SHARD, bool PTSS, bool RING, int MS, bool GRP, bool DIAG = false, bool SAMP = false>
 __device__ __forceinline__ void agg_loop_body(const MirrorView& m, const BatchView& b, const AggView& av, const int w_grp) {
   static_assert(!DIAG || !RING, "the diagnosing instances: batch runs");
+  static_assert(!SAMP || (!SHARD && !RING && !GRP && !DIAG), "the sampling instances: unsharded, undiagnosed batch runs");
   constexpr bool kPxa = RING || MS < kMaxSweep;  // phase 1 guesses the PTS raw scores (AG_PXA)
   constexpr int kBlob = RING ? kBlobLds : kAggBlobLds;       // program slot bytes (desc.h)
   constexpr uint32_t kLp = RING ? kAggRingPods : kAggPods;     // LDS list entries (the rest spill to HBM)
@@ -3566,6 +3574,12 @@ __device__ __forceinline__ void agg_loop_body(const MirrorView& m, const BatchVi
   __shared__ unsigned long long s_ball[kAggThreads / 64];  // [wave] feasibility ballots
   __shared__ uint32_t s_st[DIAG ? kAggThreads : 1];        // DIAG: [slot] phase 1's packed Filter status (0: feasible,
                                                            // or no node in the slot)
+  // SAMP (referenced by those instances only):
+  __shared__ uint32_t s_rot[SAMP ? 2 : 1];                 // nextStartNodeIndex of pod q in s_rot[q & 1]
+  __shared__ uint32_t s_samp[SAMP ? 2 : 1];                // pod q's {processedNodes, K when its list is cut (~0u: no cut)}
+  __shared__ unsigned long long s_pbl[SAMP && PTSS ? kAggThreads / 64 : 1];  // [wave] feasible, non-ignored ballots
+  __shared__ uint8_t s_pdom[SAMP && PTSS ? kAggScoreCons : 1][SAMP && PTSS ? kAggThreads : 1];  // [constraint][slot]
+                                                           // my node's domain presence bit (255: none, or hostname)
   __shared__ int32_t s_lh[kAggLocal * kAggSlots];          // node-local histograms
   __shared__ unsigned long long s_gh[kAggGWords];          // shared-region partials, then totals
   __shared__ __align__(16) uint16_t s_elig[kAggSlots];     // eligibility per node: DoNotSchedule c (bit c),
@@ -3686,6 +3700,11 @@ __device__ __forceinline__ void agg_loop_body(const MirrorView& m, const BatchVi
   // spec(q): pod q's counts may be gathered before pod q-1 is placed, and pod q-1 folded in after
   // (no node-local DoNotSchedule minimum, which would need the chosen node's own count)
   auto spec = [&](const PodDesc& dn) { return dn.agg_local_cons == 0 && !(av.debug & 1); };
+  // pod q's nextStartNodeIndex: the program's (host-side rotation), or the device's (SAMP)
+  auto rot_of = [&](const PodDesc& dq, int q) __attribute__((always_inline)) -> int {
+    if constexpr (SAMP) return (int)s_rot[q & 1];
+    else return dq.rot_start;
+  };
 
   // ---- aggregation of pod q by threads [0, nthr) of a group (tid = my index in it), meeting at
   // gbar(): the pod's selectors against my pods, my pods' terms against the pod, my nodes'
@@ -4333,6 +4352,17 @@ __device__ __forceinline__ void agg_loop_body(const MirrorView& m, const BatchVi
   if (!RING && av.npods > 1) stage_prog(1, t, kAggThreads);
   if (kTc && t < 2) s_tcr[t] = t < av.npods ? tc_word(t) : 0u;  // (then pod q+2's while pod q is decided)
   __syncthreads();
+  if constexpr (SAMP) {
+    // the run's first pod: the previous launched pod's nextStartNodeIndex, or the host's (read before phase 1
+    // of pod 0, behind the barriers of its gather)
+    if (t == 0 && av.npods > 0) {
+      const PodDesc& d0 = *reinterpret_cast<const PodDesc*>(s_blob[0]);
+      s_rot[0] = d0.prev_pod < 0 ? b.stats[av.first_pod].rot_in : b.stats[d0.prev_pod].rot_out;
+      s_rot[1] = 0u;
+      s_samp[0] = 0u;
+      s_samp[1] = ~0u;
+    }
+  }
   if (s_np > pcap || s_nt > tcap) {  // host-checked; never taken
     if (t == 0) fail(0xfffffffeu);
     return;
@@ -4576,6 +4606,10 @@ __device__ __forceinline__ void agg_loop_body(const MirrorView& m, const BatchVi
             s_pc[c][t] = cnt[c];
           }
           pts_on = feas && !ign;
+          if constexpr (SAMP && PTSS) {
+  #pragma unroll
+            for (int c = 0; c < kAggScoreCons; ++c) s_pdom[c][t] = (uint8_t)255;
+          }
           if (pts_on)
   #pragma unroll
             for (int c = 0; c < kAggScoreCons; ++c)
@@ -4583,6 +4617,7 @@ __device__ __forceinline__ void agg_loop_body(const MirrorView& m, const BatchVi
                 const int b = cs[c].pbit + pts_domain(m, cs[c], my_iq);
                 if (b < 64) pb0 |= 1ull << b;
                 else pb1 |= 1ull << (b - 64);
+                if constexpr (SAMP && PTSS) s_pdom[c][t] = (uint8_t)b;  // (< 76: exchange A's presence bits)
               }
   #pragma unroll
           for (int o = 32; o > 0; o >>= 1) {
@@ -4591,7 +4626,9 @@ __device__ __forceinline__ void agg_loop_body(const MirrorView& m, const BatchVi
           }
         }
         const unsigned long long pball = __ballot(pts_on);
-        const int lim = d.rot_start - (nlo + wave * 64);
+        if constexpr (SAMP && PTSS)
+          if (lane == 0) s_pbl[wave] = pball;
+        const int lim = rot_of(d, q) - (nlo + wave * 64);
         const unsigned long long bm = lim <= 0 ? 0ull : lim >= 64 ? ~0ull : ((1ull << lim) - 1ull);
         s_sv[t] = SlotVal{ne.fixed, (uint32_t)ne.rt, (uint32_t)ne.rna};
         s_ri[t] = ne.ripa;
@@ -4666,7 +4703,7 @@ __device__ __forceinline__ void agg_loop_body(const MirrorView& m, const BatchVi
       // q-1 (the host compared the program bytes: only the slot, the rotation and the label-pool offset differ,
       // and phase 1 reads the rotation alone): the count before the new rotation start, from the ballots
       if (lane == 0) {
-        const int lim = d.rot_start - (nlo + wave * 64);
+        const int lim = rot_of(d, q) - (nlo + wave * 64);
         const unsigned long long bm = lim <= 0 ? 0ull : lim >= 64 ? ~0ull : ((1ull << lim) - 1ull);
         s_wu[wave][1] = (uint32_t)__popcll(s_ball[wave] & bm);
       }
@@ -4743,6 +4780,110 @@ __device__ __forceinline__ void agg_loop_body(const MirrorView& m, const BatchVi
         F = wave_sum_u32(F);
         bf = wave_sum_u32(bf);
         wp = wave_sum_u32(wp);
+        bool okm = true;
+        [[maybe_unused]] uint32_t keepK = 0xffffffffu, proc = (uint32_t)m.n;  // (no cut: every node processed)
+        if constexpr (SAMP) {
+          // percentageOfNodesToScore (DF_ROTDEV): findNodesThatPassFilters keeps the first K feasible nodes of the
+          // rotated order and stops at the (K+1)-th (schedule_one.go:809-824).  F and K are the same in every
+          // workgroup, so exchange M is entered by all of them or by none.
+          const uint32_t K = (d.flags & DF_ROTDEV) ? (uint32_t)__builtin_amdgcn_readfirstlane(d.num_to_find) : 0xffffffffu;
+          if (ok && F > K) {
+            keepK = K;
+            const uint32_t gK = (bf + K) % F;  // the (K+1)-th node's global feasible index
+            const int rot = (int)s_rot[q & 1];
+            // my kept nodes (feasible, rotated position < K): what NormalizeScore and PodTopologySpread's PreScore
+            // reduce over the feasible list (k_sample_apply's reductions)
+            unsigned long long kt = 0, kn = 0, ki = 0, kni = ~0ull, kp0 = 0, kp1 = 0;
+            uint32_t kc = 0, kpn = 0, proc1 = 0, gacc = wp;
+#pragma unroll 1
+            for (int v = 0; v < kAggThreads / 64; ++v) {
+              const unsigned long long bal = s_ball[v];
+              const int ls = v * 64 + lane;
+              const bool f = ((bal >> lane) & 1ull) != 0;
+              const uint32_t g = gacc + wave_prefix_count(bal, lane);
+              const uint32_t pos = g >= bf ? g - bf : g + F - bf;
+              const bool kept = f && pos < K;
+              if (f && g == gK) proc1 = (uint32_t)(((int64_t)(nlo + ls) - (int64_t)rot + m.n) % m.n) + 1u;
+              if (kept) {
+                const SlotVal sv = s_sv[ls];
+                const unsigned long long et = enc_i64((int64_t)sv.rt), en = enc_i64((int64_t)sv.rn), ei = enc_i64(s_ri[ls]);
+                kt = et > kt ? et : kt;
+                kn = en > kn ? en : kn;
+                ki = ei > ki ? ei : ki;
+                kni = ei < kni ? ei : kni;
+                ++kc;
+                if constexpr (PTSS) {
+                  if (pts_q && ((s_pbl[v] >> lane) & 1ull)) {
+                    ++kpn;
+#pragma unroll
+                    for (int c = 0; c < kAggScoreCons; ++c) {
+                      const uint32_t pb = s_pdom[c][ls];
+                      if (pb < 64u) kp0 |= 1ull << pb;
+                      else if (pb < 128u) kp1 |= 1ull << (pb - 64u);
+                    }
+                  }
+                }
+              }
+              gacc += (uint32_t)__popcll(bal);
+            }
+            kt = wave_max_u64(kt);
+            kn = wave_max_u64(kn);
+            ki = wave_max_u64(ki);
+            kni = ~wave_max_u64(~kni);
+            kc = wave_sum_u32(kc);
+            proc1 = wave_sum_u32(proc1);  // (one lane of one workgroup holds the node)
+            if constexpr (PTSS) {
+              kpn = wave_sum_u32(kpn);
+              for (int o = 32; o > 0; o >>= 1) {
+                kp0 |= __shfl_xor(kp0, o, 64);
+                kp1 |= __shfl_xor(kp1, o, 64);
+              }
+            }
+            const int qm = q + kLoopMaxPods;  // the second bank of granule rows
+            if (lane == 0) {
+              agran_put<SHARD>(av, qm, gid, AG_A0, ((unsigned long long)proc1 << 20) | (unsigned long long)kc);
+              agran_put<SHARD>(av, qm, gid, AG_A1, gran_a_maxima(kc, kt, kn));
+              agran_put<SHARD>(av, qm, gid, AG_A2, kc ? (unsigned long long)(dec_i64(ki) + kAggIpaBias) + 1ull : 0ull);
+              agran_put<SHARD>(av, qm, gid, AG_A3, kc ? (1ull << 47) - (unsigned long long)(dec_i64(kni) + kAggIpaBias) : 0ull);
+              if (pts_q) {
+                agran_put<SHARD>(av, qm, gid, AG_P0, kp0 & ((1ull << 48) - 1ull));
+                agran_put<SHARD>(av, qm, gid, AG_P1, (unsigned long long)(kpn & 0xfffffu) |
+                                                   ((((kp0 >> 48) | (kp1 << 16)) & ((1ull << 28) - 1ull)) << 20));
+              }
+            }
+            tmax = nmax = imax = inmax = p0 = p1 = 0;
+            ni = 0;
+            unsigned long long pm = 0;
+            okm = agran_sweep<SHARD, PTSS ? 6 : 4, MS, RING || !PTSS>(av, qm, AG_A0, [&](int r, const auto& xm) {
+              if (lane + 64 * r < P) {
+                const unsigned long long pv = xm[0] >> 20;
+                pm = pv > pm ? pv : pm;
+                const unsigned long long tv = gran_a_tp1(xm[1]), nv = gran_a_np1(xm[1]);
+                tmax = tv > tmax ? tv : tmax;
+                nmax = nv > nmax ? nv : nmax;
+                imax = xm[2] > imax ? xm[2] : imax;
+                inmax = xm[3] > inmax ? xm[3] : inmax;
+                if constexpr (PTSS) {
+                  ni += (uint32_t)(xm[5] & 0xfffffull);
+                  p0 |= xm[4];
+                  p1 |= xm[5] >> 20;
+                }
+              }
+            }, pts_q ? 6 : 4);
+            pm = wave_max_u64(pm);
+            if (okm && pm == 0ull) {  // no workgroup found the (K+1)-th node: a protocol error, never a hang
+              if (lane == 0) fail(0xfffffffcu);
+              okm = false;
+            }
+            proc = pm ? (uint32_t)pm - 1u : 0u;
+            stamp(q, 9);
+          }
+          if (lane == 0) {
+            s_samp[0] = proc;
+            s_samp[1] = keepK;
+            s_rot[(q + 1) & 1] = m.n > 0 ? (uint32_t)(((uint64_t)s_rot[q & 1] + proc) % (uint64_t)m.n) : 0u;
+          }
+        }
         tmax = wave_max_u64(tmax);
         nmax = wave_max_u64(nmax);
         imax = wave_max_u64(imax);
@@ -4773,7 +4914,7 @@ __device__ __forceinline__ void agg_loop_body(const MirrorView& m, const BatchVi
           s_mx[1] = nmax ? (int64_t)nmax - 1 : 0;
           s_mx[2] = imax ? (int64_t)(imax - 1ull) - kAggIpaBias : 0;
           s_mx[3] = inmax ? (int64_t)((1ull << 47) - inmax) - kAggIpaBias : 0;
-          if (!ok) s_ok = 0u;
+          if (!ok || !okm) s_ok = 0u;
           __hip_atomic_store(&s_a_q, q, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
         }
         stamp(q, 2);
@@ -4790,6 +4931,18 @@ __device__ __forceinline__ void agg_loop_body(const MirrorView& m, const BatchVi
         // phase 1 guessed (s_psz_used), its raw scores stand and exchange A carried the max / min (AG_PXA).
         spec = kPxa && __ballot(lane < d.n_ptss && lane < kAggScoreCons && s_psz[lane] != s_psz_used[lane]) == 0ull &&
                !(av.debug & 16);
+        // SAMP, a cut list: NormalizeScore's max / min are over the kept nodes (scoring.go:229-268 iterates the
+        // feasible list), so AG_PXA's full-list values do not stand -- the scores are taken again over the kept nodes
+        [[maybe_unused]] uint32_t pK = 0xffffffffu, pacc = 0, pF = 0, pbf = 0;
+        if constexpr (SAMP) {
+          pK = s_samp[1];
+          spec = spec && pK == 0xffffffffu;
+          pacc = s_acc;
+          if (wave == 1)
+            for (int v = 0; v < kAggThreads / 128; ++v) pacc += (uint32_t)__popcll(s_ball[v]);
+          pF = s_F;
+          pbf = s_psb;
+        }
         const PtsCons* cs = at<PtsCons>(base, d.ptss_off);
         const bool anytopo = (d.flags & DF_PTS_ANYTOPO) != 0;
         double wt[kAggScoreCons];
@@ -4799,7 +4952,12 @@ __device__ __forceinline__ void agg_loop_body(const MirrorView& m, const BatchVi
 #pragma unroll
         for (int vv = 0; vv < kH && !spec; ++vv) {
           const int v = wave * kH + vv, ls = v * 64 + lane;
-          const bool f = ((s_ball[v] >> lane) & 1ull) != 0;
+          bool f = ((s_ball[v] >> lane) & 1ull) != 0;
+          if constexpr (SAMP) {  // kept: rotated position < K
+            const uint32_t g = pacc + wave_prefix_count(s_ball[v], lane);
+            f = f && (g >= pbf ? g - pbf : g + pF - pbf) < pK;
+            pacc += (uint32_t)__popcll(s_ball[v]);
+          }
           bool ign = false;
           double score = 0.0;
 #pragma unroll
@@ -4869,6 +5027,8 @@ __device__ __forceinline__ void agg_loop_body(const MirrorView& m, const BatchVi
       // feasible list, NormalizeScore + weights, the best packed key
       const bool ok = s_ok != 0u;
       const uint32_t F = s_F, ps_before = s_psb;
+      [[maybe_unused]] uint32_t cutK = 0xffffffffu;
+      if constexpr (SAMP) cutK = s_samp[1];
       const int64_t mx_t = s_mx[0], mx_n = s_mx[1], mx_i = s_mx[2], mn_i = s_mx[3];
       uint32_t acc = s_acc;
       if (wave == 1)
@@ -4903,7 +5063,9 @@ __device__ __forceinline__ void agg_loop_body(const MirrorView& m, const BatchVi
             const int64_t sc = rp[vv] == ~0u ? 0 : pmx == 0 ? 100 : go_div(100 * (pmx + pmn - (int64_t)rp[vv]), pmx);
             total += sc * d.weight[P_PTS];
           }
-          const unsigned long long kv = f ? pack_best(total, pos) : 0ull;
+          bool keep = f;
+          if constexpr (SAMP) keep = f && pos < cutK;  // the cut feasible list: the first K of the rotated order
+          const unsigned long long kv = keep ? pack_best(total, pos) : 0ull;
           knode = kv > key ? nlo + ls : knode;
           key = kv > key ? kv : key;
           acc += (uint32_t)__popcll(ballot[vv]);
@@ -5036,23 +5198,38 @@ __device__ __forceinline__ void agg_loop_body(const MirrorView& m, const BatchVi
           s_pw = pw;
           if (SHARD) s_rnode = (int)bnlo - 1;  // the chosen node (global index), for a replica's commit
           s_pend_ls = -1;
+          // SAMP: the committing thread writes the pod's rotation bookkeeping for commit_result (EvaluatedNodes,
+          // the next nextStartNodeIndex) and reports the cut list's length (k_sched_loop's rot_stats)
+          [[maybe_unused]] auto rot_stats = [&]() __attribute__((always_inline)) {
+            if constexpr (SAMP) {
+              if (d.flags & DF_ROTDEV) {
+                ps->rot = s_rot[q & 1];
+                ps->processed = s_samp[0];
+                ps->rot_out = s_rot[(q + 1) & 1];
+              }
+            }
+          };
+          uint32_t Fc = F;  // the feasible list's length
+          if constexpr (SAMP) Fc = s_samp[1] != 0xffffffffu ? s_samp[1] : F;
           if (okb) {
             if (F == 0) {
               if (w == 0) {
+                rot_stats();
                 commit_result(m, b, base, d, ps, pod, 0, -1, gbest, nullptr, (int)ipa_any);
                 if constexpr (RING) ring_post_p(av.ring, q, b.results[pod]);
               }
             } else if (gnode >= nlo && gnode < nhi) {
               const int ls = gnode - nlo;
+              rot_stats();
               if (d.flags & DF_ASSUME) {
                 NodeCore c = lds_core(s_core, ls / kBlock, ls % kBlock);
                 assume_core(c, d);
-                commit_result(m, b, base, d, ps, pod, F, gnode, gbest, &c, (int)ipa_any);
+                commit_result(m, b, base, d, ps, pod, Fc, gnode, gbest, &c, (int)ipa_any);
                 lds_put_dynamic(s_core, ls / kBlock, ls % kBlock, c);
                 if (d.slot >= 0) s_pend_ls = ls;
                 if constexpr (RING) apply_entry(m, s_blob[(q + 1) % 3]);
               } else {
-                commit_result(m, b, base, d, ps, pod, F, gnode, gbest, nullptr, (int)ipa_any);
+                commit_result(m, b, base, d, ps, pod, Fc, gnode, gbest, nullptr, (int)ipa_any);
               }
               if constexpr (RING) ring_post_p(av.ring, q, b.results[pod]);
             }
@@ -7179,6 +7356,48 @@ hipError_t loop_occupancy_nom(int (&occ)[2]) {
     const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&o, q.f, q.threads, 0);
     if (e != hipSuccess) return e;
     occ[q.k] = o < occ[q.k] ? o : occ[q.k];
+  }
+  return hipSuccess;
+}
+
+// k_agg_loop's sampling instances (agg_loop_body's SAMP; config "aggLoopSampled"): the twins of the four unsharded
+// batch instances launch_agg_loop picks among, for runs of DF_ROTDEV pods.  Kernels of their own, defined behind
+// every other kernel: the instances above keep their names and their place in the code object.
+template <bool PTSS, int MS>
+__global__ __launch_bounds__(kAggThreads) void k_agg_loop_samp(MirrorView m, BatchView b, AggView av) {
+  const AggGroupArg& a = *(const AggGroupArg*)__builtin_amdgcn_kernarg_segment_ptr();  // (k_sched_loop)
+  agg_loop_body<false, PTSS, false, MS, false, false, true>(a.m, a.b, a.av, 0);
+}
+hipError_t launch_agg_loop_samp(const MirrorView& m, const BatchView& b, const AggView& av, hipStream_t s, hipEvent_t t0,
+                                hipEvent_t t1) {
+  if (av.ring != nullptr || av.world > 1 || av.diag != nullptr) return hipErrorInvalidValue;
+  auto go = [&](auto kern) {
+    if (t0)
+      hipExtLaunchKernelGGL(kern, dim3(av.nwg), dim3(kAggThreads), 0, s, t0, t1, 0, m, b, av);
+    else
+      hipLaunchKernelGGL(kern, dim3(av.nwg), dim3(kAggThreads), 0, s, m, b, av);
+  };
+  if (av.ptss && av.nwg <= 64) go(k_agg_loop_samp<true, 1>);
+  else if (av.ptss) go(k_agg_loop_samp<true, kMaxSweep>);
+  else if (av.nwg <= 64) go(k_agg_loop_samp<false, 1>);
+  else go(k_agg_loop_samp<false, kMaxSweep>);
+  return hipGetLastError();
+}
+// their code loaded before the first batch (warm_kernels), and the workgroups of the largest of them one CU holds
+hipError_t agg_samp_occupancy(int* occ) {
+  const void* fs[] = {reinterpret_cast<const void*>(&k_agg_loop_samp<true, 1>),
+                      reinterpret_cast<const void*>(&k_agg_loop_samp<true, kMaxSweep>),
+                      reinterpret_cast<const void*>(&k_agg_loop_samp<false, 1>),
+                      reinterpret_cast<const void*>(&k_agg_loop_samp<false, kMaxSweep>)};
+  *occ = 1 << 30;
+  for (const void* f : fs) {
+    hipFuncAttributes a;
+    hipError_t e = hipFuncGetAttributes(&a, f);
+    if (e != hipSuccess) return e;
+    int o = 0;
+    e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&o, f, kAggThreads, 0);
+    if (e != hipSuccess) return e;
+    *occ = o < *occ ? o : *occ;
   }
   return hipSuccess;
 }

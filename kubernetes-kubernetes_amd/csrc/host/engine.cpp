@@ -107,6 +107,10 @@ hipError_t launch_diag_reduce(const MirrorView& m, const BatchView& b, int pod, 
                               int nblk = -1);
 hipError_t launch_ob_remap(ObState* st, ObEnt* h, const int32_t* map, int nold, int maxlen, hipStream_t s);
 hipError_t loop_occupancy(int (&occ)[4]);
+// k_agg_loop's sampling instances (a run of DF_ROTDEV pods, config "aggLoopSampled")
+hipError_t launch_agg_loop_samp(const MirrorView& m, const BatchView& b, const AggView& av, hipStream_t s, hipEvent_t t0,
+                                hipEvent_t t1);
+hipError_t agg_samp_occupancy(int* occ);
 
 #define HIPCHK(x)                                               \
   do {                                                          \
@@ -1049,7 +1053,8 @@ Engine::Engine(Cluster* cl) : c(cl) {
   // every kernel's code object loaded before the first batch (see warm_kernels)
   if (c->err.empty() && (warm_kernels() != hipSuccess || warm_aggregate() != hipSuccess || warm_kernels_nom() != hipSuccess))
     c->err = "cannot load the kernels' code object on HIP device " + std::to_string(c->cfg.device);
-  if (c->err.empty() && (loop_occupancy(loop_occ) != hipSuccess || loop_occupancy_nom(loop_occ_nom) != hipSuccess))
+  if (c->err.empty() && (loop_occupancy(loop_occ) != hipSuccess || loop_occupancy_nom(loop_occ_nom) != hipSuccess ||
+                         agg_samp_occupancy(&agg_samp_occ) != hipSuccess))
     c->err = "cannot query the persistent loops' occupancy on HIP device " + std::to_string(c->cfg.device);
 }
 
@@ -1203,13 +1208,20 @@ bool Engine::loop_ok(const CompiledPod& p) const {
   if ((d.flags & DF_ROTDEV) && (comm || (d.flags & (DF_SUBSET | DF_PREFILTER_REJECT)))) return false;
   return loop_bounds_ok(p);
 }
-// A pod k_agg_loop takes: any CYCLE pod without evaluation output, PreFilter outcomes or sampling, whose
-// histograms and PodTopologySpread score constraints fit the loop's placement (CompiledPod::agg_ok).
-bool Engine::agg_loop_ok(const CompiledPod& p) const {
+// A pod k_agg_loop takes: any CYCLE pod without evaluation output or PreFilter outcomes, whose histograms and
+// PodTopologySpread score constraints fit the loop's placement (CompiledPod::agg_ok).
+bool Engine::agg_loop_ok(const CompiledPod& p, bool resident) const {
   if (p.error || !p.agg_ok || p.blob.size() > (size_t)kAggBlobLds) return false;
   const PodDesc& d = *reinterpret_cast<const PodDesc*>(p.blob.data());
-  if (d.flags & (DF_EVAL_OUT | DF_SCORE_ERROR | DF_ALL_FEASIBLE | DF_ROTDEV | DF_PREFILTER_REJECT | DF_SUBSET | DF_EARLY |
-                 DF_NOM_TOPO))
+  if (d.flags & (DF_EVAL_OUT | DF_SCORE_ERROR | DF_ALL_FEASIBLE | DF_PREFILTER_REJECT | DF_SUBSET | DF_EARLY | DF_NOM_TOPO))
+    return false;
+  // sampled pods (percentageOfNodesToScore / no-score profiles / a nominated pod in the batch): the loop's sampling
+  // instances cut the list and carry nextStartNodeIndex themselves, under loop_ok's rule -- batch
+  // runs, unsharded, over the whole snapshot (DF_SUBSET / DF_PREFILTER_REJECT are refused above) -- and undiagnosed
+  // (a diagnosed batch's sampled pods keep the launch path and k_diag_reduce); their residency is the other
+  // instances' (run_batch checks loop_occ[2])
+  if ((d.flags & DF_ROTDEV) &&
+      (!c->cfg.agg_loop_sampled || resident || comm || (d.flags & DF_DIAG) || agg_samp_occ < loop_occ[2]))
     return false;
   // the fold plan holds <= 8 items per kind of the next pod's constraints / terms plus one per own
   // term of the pod just placed (kFoldMax = 80 in k_agg_loop)
@@ -1417,7 +1429,10 @@ int Engine::gran_setup() {
 // granules and adds its shared-key partials into every rank's copy.
 int Engine::agg_setup() {
   if (!agran_all.empty()) return KSG_OK;
-  const size_t gb = (size_t)(kLoopMaxPods + 1) * 256 * kAGran * 8, rb = (size_t)kLoopMaxPods * kAggGWords * 8;
+  // (unsharded with "aggLoopSampled": 2 kLoopMaxPods rows -- a sampled pod q's exchange M sits at q + kLoopMaxPods,
+  // as k_sched_loop's)
+  const size_t rows = !comm && c->cfg.agg_loop_sampled ? (size_t)2 * kLoopMaxPods : (size_t)kLoopMaxPods + 1;
+  const size_t gb = rows * 256 * kAGran * 8, rb = (size_t)kLoopMaxPods * kAggGWords * 8;
   for (DevBuf* b : {&d_agran, &d_region}) {
     const size_t bytes = b == &d_agran ? gb : rb;
     if (b->p) (void)hipFree(b->p);
@@ -2524,7 +2539,7 @@ int Engine::run_batch(const std::vector<const PodSpec*>& pods, const std::vector
     (void)hipStreamSynchronize(s);
     if (f[1] >= 0xfffffff0u)  // k_agg_loop's own checks (list capacity): the first failure is kept
       return "persistent loop stopped: workgroup " + std::to_string(f[2]) + " failed check " + std::to_string(0xffffffffu - f[1]) +
-             " (1: its pod / term lists exceed their capacity at launch, 2: an append overflowed)";
+             " (1: its pod / term lists exceed their capacity at launch, 2: an append overflowed, 3: no workgroup held a cut list's end node)";
     const bool agg = f[4] == 2;
     const int g = agg ? G : GS, ng = agg ? kAGran : kGran;
     std::vector<unsigned long long> row((size_t)W * g * ng);
@@ -2676,10 +2691,11 @@ int Engine::run_batch(const std::vector<const PodSpec*>& pods, const std::vector
       double rb = 0;
       int32_t gw = 1;
       const int cut = chunk_end(i);
-      bool ptss = false;
+      bool ptss = false, samp = false;  // samp: sampled pods (rotdev() is per batch: all of the run, or none)
       while (j < n && j < cut && j - i < kLoopMaxPods && agg_loop_ok(cp[j]) && !loop_ok(cp[j])) {
         const PodDesc& hd = *reinterpret_cast<const PodDesc*>(cp[j].blob.data());
         ptss = ptss || ((hd.score_mask >> P_PTS) & 1u) || hd.n_ptss > 0;
+        samp = samp || (hd.flags & DF_ROTDEV) != 0;
         rb += algo_bytes(hd) + agg_bytes(hd);
         gw = std::max(gw, hd.agg_gwords);
         ++j;
@@ -2755,6 +2771,8 @@ int Engine::run_batch(const std::vector<const PodSpec*>& pods, const std::vector
         req.t0 = t0;
         req.t1 = t1;
         if ((rc = group_launch(&req, true, G, 0))) return rc;
+      } else if (samp) {
+        HIPCHK(launch_agg_loop_samp(m, bv, av, s, t0, t1));
       } else {
         HIPCHK(launch_agg_loop(m, bv, av, s, t0, t1));
       }
@@ -3536,7 +3554,7 @@ int Engine::schedule_resident(const PodSpec& p, int32_t handle, ksg_result* res,
   int kind = 0;
   if (!cp.error && !cp.prefilter_reject && cp.blob.size() % 16 == 0) {
     const bool sched_ok = sched_geo && loop_ok(cp);
-    const bool agg_ok = agg_geo && agg_loop_ok(cp) && cp.own_terms <= 4 * kAggMaxTerms;
+    const bool agg_ok = agg_geo && agg_loop_ok(cp, true) && cp.own_terms <= 4 * kAggMaxTerms;
     if (agg_ok && (!sched_ok || (res_running_ && res_kind_ == 2))) kind = 2;
     else if (sched_ok) kind = 1;
   }

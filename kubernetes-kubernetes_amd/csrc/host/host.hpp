@@ -241,6 +241,9 @@ struct Config {
   // k_sched_loop: the lean path for DF_RAW0 pods ("loopLeanSelect": true / false, or a mask of its parts for
   // measurements: desc.h kLeanA | kLeanP2 | kLeanP1)
   int loop_lean_select = kLeanAll;
+  // k_agg_loop: batch runs of sampled pods (DF_ROTDEV: percentageOfNodesToScore < 100, a no-score profile, a
+  // nominated pod in the batch) through its sampling instances ("aggLoopSampled"; false: the launch path, as before)
+  bool agg_loop_sampled = true;
   bool resident_ahead = true;  // resident loops: the next pod's phase 1 ahead of its doorbell (LoopView, AggView bit 7)
   int debug_give_up_at = -1;    // diagnostic: the persistent loops give up at this pod of a run
   int loop_wg = 0;              // k_sched_loop workgroups (0: min(node units, CUs, 128))
@@ -650,9 +653,11 @@ class Engine {
   // ... of the in-process groups' k_sched_loop with the nominee overlay (loop_occupancy_nom: by unit), which a
   // group launches when a nominee table is staged
   int loop_occ_nom[2] = {0, 0};
+  int agg_samp_occ = 0;  // ... of k_agg_loop's sampling instances (agg_samp_occupancy), which a run of sampled pods takes
   bool loop_ok(const CompiledPod& p) const;
   bool loop_bounds_ok(const CompiledPod& p) const;  // the loops' granule payload bounds
-  bool agg_loop_ok(const CompiledPod& p) const;
+  // resident: a resident one-pod call (the ring's instance carries no sampling)
+  bool agg_loop_ok(const CompiledPod& p, bool resident = false) const;
   // node-sharded evaluation (cfg.world > 1): this rank's block range + the exchange transport
   std::unique_ptr<Comm> comm;
   int32_t next_slot_ = -1;  // compile(): a pod-table slot reserved by run_batch's pipeline
