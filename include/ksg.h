@@ -441,6 +441,18 @@ int ksg_debug_group_loop_kernel(char *buf, size_t cap);
  * the host; both stay 0 with the key off. */
 int ksg_debug_lean_pods(const ksg_ctx *ctx, uint64_t *lean, uint64_t *general);
 
+/* k_sched_same (config "loopSameTemplate", default true; "loopSameMinRun"): of the pods of
+ * k_sched_loop's runs since the context was created, those that went to k_sched_same -- stretches of at least
+ * loopSameMinRun eligible pods stamped from one template, on an unsharded context of at most 8192 nodes without a
+ * nominee table, a diagnosis or loopStamps -- (*taken) and those k_sched_loop ran (*not_taken).  Counted on the
+ * host. */
+int ksg_debug_same_pods(const ksg_ctx *ctx, uint64_t *taken, uint64_t *not_taken);
+
+/* The host's same-template predicate on two queued pods (ksg_compile handles), compiled as a batch with
+ * KSG_FLAG_ASSUME compiles them: 1 when pod b may follow pod a in a k_sched_same run (both eligible, one program
+ * but for slot, rotation start and batch bookkeeping), 0 when not, negative on error.  Schedules nothing. */
+int ksg_debug_sched_same(ksg_ctx *ctx, int32_t handle_a, int32_t handle_b);
+
 /* Sampled pods in k_agg_loop (config "aggLoopSampled", default true; DESIGN.md §4.5 "Inside k_agg_loop").  In a
  * context whose nextStartNodeIndex lives on the device -- percentageOfNodesToScore other than 100 (0, upstream's
  * adaptive default, included), a profile without score plugins, OpportunisticBatching acting, or a batch holding a pod

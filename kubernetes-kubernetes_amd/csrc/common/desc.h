@@ -726,6 +726,23 @@ constexpr int kGran = 16;
 constexpr int kFailWords = 16;
 constexpr int kFailBytes = kFailWords * 4;
 
+// ---- k_sched_same: a run of pods stamped from one template, selected from cached evaluations
+// by ONE workgroup -- no granules, no cross-workgroup exchange.  It takes a LoopView (first_pod, npods, fail,
+// desc_bytes; the rest unused).  kSameScanWaves waves hold the packed keys of their nodes in registers (node
+// i = slot * kSameScanWaves * 64 + scan thread) and pick each pod's winner; kSameCommitWaves waves (node % kSameCommitWaves)
+// store the winner's AssumePod and evaluate the node again behind the selection's back.
+constexpr int kSameScanWaves = 8, kSameCommitWaves = 8;
+constexpr int kSameThreads = (kSameScanWaves + kSameCommitWaves) * 64;
+constexpr int kSameSlots = 16;                                        // node slots per scan lane
+constexpr int kSameMaxNodes = kSameSlots * kSameScanWaves * 64;       // 8192
+constexpr int kSameGroups = kSameMaxNodes / 64;                       // 64-node ballot groups
+// LDS: the program, per node the post-assume fixed score (8 B) and a pending byte, per group the two ballots,
+// per pod its slot, rotation start and decided {key, node, F}
+constexpr int kSameLdsBytes = kBlobLds + kSameMaxNodes * (8 + 1) + kSameGroups * 16 + kLoopMaxPods * (4 + 4 + 16) + 256;
+static_assert(kSameLdsBytes <= 160 * 1024, "k_sched_same: one workgroup's LDS (160 KiB per CU on gfx950)");
+static_assert(kSameGroups <= 128, "k_sched_same: the group prefix scan holds two groups per lane");
+static_assert(kSameMaxNodes >= 5000, "k_sched_same: the flagship workload's nodes fit");
+
 // ---- persistent loop for pods with pod-table aggregation (k_agg_loop) ---------------
 // Same workgroup geometry as k_sched_loop (unsharded).  Each workgroup also owns the pod-table slots
 // and existing affinity terms of the pods bound to its nodes.

@@ -7402,4 +7402,330 @@ hipError_t agg_samp_occupancy(int* occ) {
   return hipSuccess;
 }
 
+// =====================================================================================================
+// k_sched_same -- a run of pods stamped from one template, selected from cached evaluations
+// =====================================================================================================
+// The run's pods share one program but for their slot and rotation start (host: sched_same), are DF_FAST | DF_RAW0
+// and assume no host port: everything phase 1 produces for a node depends on that node's own columns only, and an
+// AssumePod changes one node.  One workgroup keeps, per node, the packed key of the node as it is (scan waves,
+// registers) and the fixed score and feasibility of the node with one more template pod assumed ("post", LDS).  Per
+// pod: the maximum over the keys (what phase2_lean and exchange B's maximum give), the winner's key := its post
+// evaluation, and -- on a commit wave, behind the selection's back -- the AssumePod's stores and a fresh post
+// evaluation of that node.  No s_barrier after the fill: the scan waves meet at an LDS arrival counter per pod.
+// Every wait is bounded; a give-up is recorded in LoopView::fail as k_sched_loop's.
+struct SameLds {
+  __attribute__((aligned(16))) uint8_t blob[kBlobLds];
+  int64_t fx1[kSameMaxNodes];                      // post: weighted fixed score
+  unsigned long long ball0[kSameGroups];           // feasibility, as it is (written by the group's scan wave only)
+  unsigned long long ball1[kSameGroups];           // feasibility, post (commit waves: LDS atomics)
+  unsigned long long res_key[kLoopMaxPods];        // pod q decided: the winning key (0: no feasible node),
+  int32_t res_node[kLoopMaxPods];                  // its node (-1: none)
+  uint32_t res_F[kLoopMaxPods];                    // and the feasible list's length
+  int32_t slot[kLoopMaxPods], rot[kLoopMaxPods];   // the pods' own fields
+  unsigned long long wkey[2][kSameScanWaves];      // [pod parity] a scan wave's best key
+  uint32_t wnode[2][kSameScanWaves];               // its node | the node's post feasibility << 31
+  uint32_t arrive, arrive2, done, abort;           // scan waves arrived (per pod / per rebuild), pods decided
+  uint8_t pend[kSameMaxNodes];                     // 1: the node's post evaluation is on its way
+};
+static_assert(sizeof(SameLds) <= (size_t)kSameLdsBytes, "k_sched_same: LDS layout (desc.h kSameLdsBytes)");
+
+// bounded wait for an LDS word to reach `want` (~2 s of the 100 MHz clock); false: gave up or another wave did
+__device__ __forceinline__ bool same_wait(SameLds& L, const uint32_t* word, uint32_t want, uint32_t* fail, int q, int what) {
+  if ((int32_t)(__hip_atomic_load(word, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) - want) >= 0) return true;
+  const unsigned long long t_start = __builtin_amdgcn_s_memrealtime();
+  for (uint32_t spins = 1;; ++spins) {
+    if ((int32_t)(__hip_atomic_load(word, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) - want) >= 0) return true;
+    if ((spins & 63u) == 0u) {
+      if (__hip_atomic_load(&L.abort, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) return false;
+      if (__builtin_amdgcn_s_memrealtime() - t_start > 200000000ull) {
+        if ((threadIdx.x & 63) == 0) {
+          __hip_atomic_store(&L.abort, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+          __hip_atomic_store(fail + 1, (uint32_t)q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          __hip_atomic_store(fail + 2, (uint32_t)what, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          __hip_atomic_store(fail + 3, (uint32_t)(threadIdx.x >> 6), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          __hip_atomic_store(fail + 4, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          give_up_record(fail);
+          __hip_atomic_store(fail, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+        return false;
+      }
+    }
+    __builtin_amdgcn_s_sleep(1);
+  }
+}
+__device__ __forceinline__ bool same_wait_pend(SameLds& L, int node, uint32_t* fail, int q) {
+  const uint8_t* p = &L.pend[node];
+  if (__hip_atomic_load(p, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) == 0) return true;
+  const unsigned long long t_start = __builtin_amdgcn_s_memrealtime();
+  for (uint32_t spins = 1;; ++spins) {
+    if (__hip_atomic_load(p, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) == 0) return true;
+    if ((spins & 63u) == 0u) {
+      if (__hip_atomic_load(&L.abort, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) return false;
+      if (__builtin_amdgcn_s_memrealtime() - t_start > 200000000ull) {
+        if ((threadIdx.x & 63) == 0) {
+          __hip_atomic_store(&L.abort, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+          __hip_atomic_store(fail + 1, (uint32_t)q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          __hip_atomic_store(fail + 2, 3u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          __hip_atomic_store(fail + 3, (uint32_t)node, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          __hip_atomic_store(fail + 4, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          give_up_record(fail);
+          __hip_atomic_store(fail, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+        return false;
+      }
+    }
+    __builtin_amdgcn_s_sleep(1);
+  }
+}
+// node i with k template pods assumed on top of the mirror's columns, evaluated as phase 1 does
+__device__ __forceinline__ NodeEval same_eval(const MirrorView& m, NodeCore c, int k, const PodFast& pf, const uint8_t* base,
+                                              const PodDesc& d, int i) {
+  for (int a = 0; a < k; ++a) assume_core(c, d);
+  return eval_core_fast<false>(m, c, bal2(c.rcpu, c.acpu, c.rmem, c.amem), pf, base, d, i);
+}
+
+// (a template: its instance is emitted behind every plain kernel, with the other loops' instances -- see k_text_phase_pad)
+template <int kUnused>
+__global__ __launch_bounds__(kSameThreads) void k_sched_same(MirrorView m_, BatchView b_, LoopView lv_) {
+  const LoopGroupArg& ka = *(const LoopGroupArg*)__builtin_amdgcn_kernarg_segment_ptr();  // (k_sched_loop)
+  const MirrorView& m = ka.m;
+  const BatchView& b = ka.b;
+  const LoopView& lv = ka.lv;
+  __shared__ SameLds L;
+  constexpr int kScanThreads = kSameScanWaves * 64;
+  const int tid = (int)threadIdx.x, lane = tid & 63;
+  const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const bool scan = wv < kSameScanWaves;
+  const int npods = lv.npods;
+  loop_entry_record(lv.fail, 0);
+  // ---- the run's one program, and every pod's own fields
+  {
+    const uint32_t off0 = b.desc_off[lv.first_pod];
+    const uint4* src = reinterpret_cast<const uint4*>(b.descs + off0);
+    uint4* dst = reinterpret_cast<uint4*>(L.blob);
+    const uint32_t n16 = lv.desc_bytes[lv.first_pod] / 16u;  // <= kBlobLds / 16 (host-checked)
+    for (uint32_t o = (uint32_t)tid; o < n16; o += (uint32_t)kSameThreads) dst[o] = src[o];
+    for (int k = tid; k < npods; k += kSameThreads) {
+      const PodDesc* pd = reinterpret_cast<const PodDesc*>(b.descs + b.desc_off[lv.first_pod + k]);
+      L.slot[k] = pd->slot;
+      L.rot[k] = pd->rot_start;
+    }
+    for (int k = tid; k < kSameGroups; k += kSameThreads) L.ball0[k] = L.ball1[k] = 0ull;
+    for (int k = tid; k < kSameMaxNodes; k += kSameThreads) L.pend[k] = 0;
+    if (tid == 0) L.arrive = L.arrive2 = L.done = L.abort = 0u;
+  }
+  __syncthreads();
+  // commit_result stores pod_node[d.slot]: the shared program carries none, each pod's own is stored beside it
+  if (tid == 0) reinterpret_cast<PodDesc*>(L.blob)->slot = -1;
+  __syncthreads();
+  const uint8_t* base = L.blob;
+  const PodDesc& d = *reinterpret_cast<const PodDesc*>(base);
+  const PodFast pf = load_fast(base, d);
+  // NormalizeScore's constant of a DF_RAW0 pod (phase2_lean's `add`)
+  const int64_t add = ((d.score_mask >> P_TAINT) & 1u) ? 100 * d.weight[P_TAINT] : 0;
+  const int n = m.n;  // <= kSameMaxNodes (host-checked)
+
+  // ---- fill: scan thread t evaluates its nodes as they are, commit thread t the same nodes with one pod assumed
+  unsigned long long key[kSameSlots];  // scan lanes: pack_best(total, position) of my nodes, 0: infeasible
+  const int st = scan ? tid : tid - kScanThreads;
+#pragma unroll
+  for (int j = 0; j < kSameSlots; ++j) {
+    key[j] = 0ull;
+    const int g0 = j * kScanThreads + (st & ~63);  // my group's first node (uniform)
+    if (g0 < n) {
+      const int i = g0 + lane;
+      NodeEval ne{1u, false, 0, 0, 0, 0};
+      if (i < n) ne = same_eval(m, load_core<false>(m, i), scan ? 0 : 1, pf, base, d, i);
+      const unsigned long long bl = __ballot(ne.st == 0);
+      if (scan) {
+        key[j] = ne.st == 0 ? pack_best(ne.fixed + add, 0u) : 0ull;  // (the position: rebuild below)
+        if (lane == 0) L.ball0[g0 >> 6] = bl;
+      } else {
+        if (i < n) L.fx1[i] = ne.fixed;
+        if (lane == 0) L.ball1[g0 >> 6] = bl;
+      }
+    }
+  }
+  __syncthreads();
+
+  if (!scan) {
+    // ======== commit waves: wave c stores the AssumePod of the winners n with n % kSameCommitWaves == c (one
+    // thread per node for the whole launch: its loads of a node's columns follow its own stores to them in program
+    // order) and evaluates the node with one more pod assumed; the pods without a feasible node are wave 0's
+    const int c = wv - kSameScanWaves;
+    for (int q = 0; q < npods; ++q) {
+      if (!same_wait(L, &L.done, (uint32_t)(q + 1), lv.fail, q, 2)) return;
+      const int node = L.res_node[q];
+      if (node >= 0 ? (node % kSameCommitWaves) != c : c != 0) continue;
+      if (lane == 0) {
+        const int pod = lv.first_pod + q;
+        const uint32_t F = L.res_F[q];
+        const unsigned long long best = L.res_key[q];
+        const int ipa = (int)b.stats[pod].ipa_any;
+        if (node < 0) {
+          commit_result(m, b, base, d, b.stats + pod, pod, 0u, -1, best, nullptr, ipa);
+        } else {
+          NodeCore after = load_core<false>(m, node);
+          assume_core(after, d);
+          commit_result(m, b, base, d, b.stats + pod, pod, F, node, best, &after, ipa);
+          const int slot = L.slot[q];
+          if (slot >= 0) m.pod_node[slot] = node;
+          const NodeEval ne = same_eval(m, after, 1, pf, base, d, node);
+          L.fx1[node] = ne.fixed;
+          const unsigned long long bit = 1ull << (node & 63);
+          if (ne.st == 0) __hip_atomic_fetch_or(&L.ball1[node >> 6], bit, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+          else __hip_atomic_fetch_and(&L.ball1[node >> 6], ~bit, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+          __hip_atomic_store(&L.pend[node], (uint8_t)0, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
+        }
+      }
+    }
+    return;
+  }
+
+  // ======== scan waves
+  // Positions: ex0 / ex1 = feasible nodes before groups lane / lane + 64, F = all of them; psb = those before the
+  // pod's rotation start.  The keys hold a node's position in the rotated feasible list, so they are rebuilt
+  // whenever a ballot (hence F) or psb changes; every wave does it for itself from the ballots.
+  uint32_t ex0 = 0, ex1 = 0, F = 0, psb_cur = 0;
+  auto scan_groups = [&]() __attribute__((always_inline)) {
+    const uint32_t c0 = (uint32_t)__popcll(L.ball0[lane]);
+    const uint32_t c1 = lane + 64 < kSameGroups ? (uint32_t)__popcll(L.ball0[(lane + 64) % kSameGroups]) : 0u;
+    uint32_t i0 = c0, i1 = c1;  // inclusive scans
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+      const uint32_t a0 = __shfl_up(i0, o, 64), a1 = __shfl_up(i1, o, 64);
+      if (lane >= o) {
+        i0 += a0;
+        i1 += a1;
+      }
+    }
+    const uint32_t t0 = (uint32_t)__builtin_amdgcn_readlane((int)i0, 63);
+    ex0 = i0 - c0;
+    ex1 = t0 + i1 - c1;
+    F = t0 + (uint32_t)__builtin_amdgcn_readlane((int)i1, 63);
+  };
+  auto before = [&](int grp) __attribute__((always_inline)) -> uint32_t {  // grp uniform, < kSameGroups
+    return grp < 64 ? (uint32_t)__builtin_amdgcn_readlane((int)ex0, grp) : (uint32_t)__builtin_amdgcn_readlane((int)ex1, grp - 64);
+  };
+  auto psb_of = [&](int rot) __attribute__((always_inline)) -> uint32_t {  // feasible nodes i < rot (uniform)
+    if (rot <= 0) return 0u;
+    if (rot >= kSameMaxNodes) return F;
+    const int grp = __builtin_amdgcn_readfirstlane(rot >> 6);
+    const unsigned long long msk = (1ull << (rot & 63)) - 1ull;
+    return before(grp) + (uint32_t)__popcll(L.ball0[grp] & msk);
+  };
+  auto rebuild = [&](uint32_t psb) __attribute__((always_inline)) {
+    const unsigned long long lt = (1ull << lane) - 1ull;
+#pragma unroll
+    for (int j = 0; j < kSameSlots; ++j) {
+      const int grp = j * kSameScanWaves + wv;
+      const unsigned long long bl = L.ball0[grp];
+      const uint32_t g = before(grp) + (uint32_t)__popcll(bl & lt);
+      const uint32_t pos = g >= psb ? g - psb : g + F - psb;
+      key[j] = ((bl >> lane) & 1ull) ? pack_best((int64_t)(key[j] >> kPreBits), pos) : 0ull;
+    }
+    psb_cur = psb;
+  };
+  scan_groups();
+  rebuild(psb_of(npods > 0 ? L.rot[0] : 0));
+  bool dirty = true;         // my wave's best must be formed again
+  unsigned long long wk = 0;  // my wave's best key, its node and that node's post feasibility
+  int wn = -1;
+  uint32_t wpb = 0;
+  uint32_t nflip = 0;
+  for (int q = 0; q < npods; ++q) {
+    const int par = q & 1;
+    const uint32_t psb = psb_of(__builtin_amdgcn_readfirstlane(L.rot[q]));
+    if (psb != psb_cur) {
+      rebuild(psb);
+      dirty = true;
+    }
+    if (dirty) {
+      unsigned long long k = 0;
+      int kj = 0;
+#pragma unroll
+      for (int j = 0; j < kSameSlots; ++j) {
+        kj = key[j] > k ? j : kj;
+        k = key[j] > k ? key[j] : k;
+      }
+      wk = wave_max_u64(k);
+      const unsigned long long hold = __ballot(k == wk && k != 0ull);  // keys are unique
+      wn = -1;
+      wpb = 0;
+      if (hold) {
+        const int hl = (int)__builtin_ctzll(hold);
+        wn = __builtin_amdgcn_readlane(kj, hl) * kScanThreads + wv * 64 + hl;
+        // the node's post evaluation: final once nothing is pending for it (only this wave sets pend for its nodes)
+        if (!same_wait_pend(L, wn, lv.fail, q)) return;
+        wpb = (uint32_t)((L.ball1[wn >> 6] >> (wn & 63)) & 1ull);
+      }
+      dirty = false;
+    }
+    if (lane == 0) {
+      L.wkey[par][wv] = wk;
+      L.wnode[par][wv] = (uint32_t)wn | (wpb << 31);
+      __hip_atomic_fetch_add(&L.arrive, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
+    }
+    if (!same_wait(L, &L.arrive, (uint32_t)kSameScanWaves * (uint32_t)(q + 1), lv.fail, q, 0)) return;
+    // the run's winner: every wave reads the same words, so all decide alike
+    unsigned long long gk = 0;
+    uint32_t gn = 0xffffffffu;
+#pragma unroll
+    for (int v = 0; v < kSameScanWaves; ++v) {
+      const unsigned long long kv = L.wkey[par][v];
+      const uint32_t nv = L.wnode[par][v];
+      gn = kv > gk ? nv : gn;
+      gk = kv > gk ? kv : gk;
+    }
+    gk = ((unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(gk >> 32)) << 32) |
+         (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)gk);
+    gn = (uint32_t)__builtin_amdgcn_readfirstlane((int)gn);
+    if (gk == 0ull) {  // no feasible node: nothing changes, the pods after it see the same
+      if (wv == 0 && lane == 0) {
+        L.res_key[q] = 0ull;
+        L.res_node[q] = -1;
+        L.res_F[q] = 0u;
+        __hip_atomic_store(&L.done, (uint32_t)(q + 1), __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
+      }
+      continue;
+    }
+    const int win = (int)(gn & 0x7fffffffu);
+    const bool stays = (gn >> 31) != 0u;  // the winner is still feasible with this pod on it
+    const int wslot = win % kScanThreads;
+    if ((wslot >> 6) == wv) {  // mine: its key := its post evaluation, same position
+      const int wj = win / kScanThreads;
+      const unsigned long long nk =
+          stays ? ((unsigned long long)(L.fx1[win] + add) << kPreBits) | (gk & ((1ull << kPreBits) - 1ull)) : 0ull;
+      const bool me = lane == (wslot & 63);
+#pragma unroll
+      for (int j = 0; j < kSameSlots; ++j) key[j] = me && j == wj ? nk : key[j];
+      if (me) {
+        if (!stays) L.ball0[win >> 6] &= ~(1ull << (win & 63));
+        L.pend[win] = 1;
+        L.res_key[q] = gk;
+        L.res_node[q] = win;
+        L.res_F[q] = F;
+        __hip_atomic_store(&L.done, (uint32_t)(q + 1), __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
+      }
+      dirty = true;
+    }
+    if (!stays) {  // a ballot changed: once its owner has stored it, every wave rebuilds its positions
+      ++nflip;
+      if (lane == 0) __hip_atomic_fetch_add(&L.arrive2, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
+      if (!same_wait(L, &L.arrive2, (uint32_t)kSameScanWaves * nflip, lv.fail, q, 1)) return;
+      scan_groups();
+      rebuild(psb_of(__builtin_amdgcn_readfirstlane(L.rot[q + 1 < npods ? q + 1 : q])));
+      dirty = true;
+    }
+  }
+}
+hipError_t launch_sched_same(const MirrorView& m, const BatchView& b, const LoopView& lv, hipStream_t s, hipEvent_t t0,
+                             hipEvent_t t1) {
+  if (lv.npods < 1 || lv.npods > kLoopMaxPods || m.n > kSameMaxNodes || m.nom != nullptr || lv.ring != nullptr)
+    return hipErrorInvalidValue;
+  if (t0) hipExtLaunchKernelGGL(k_sched_same<0>, dim3(1), dim3(kSameThreads), 0, s, t0, t1, 0, m, b, lv);
+  else hipLaunchKernelGGL(k_sched_same<0>, dim3(1), dim3(kSameThreads), 0, s, m, b, lv);
+  return hipGetLastError();
+}
+
 }  // namespace ksg

@@ -604,6 +604,33 @@ int ksg_debug_lean_pods(const ksg_ctx* ctx, uint64_t* lean, uint64_t* general) {
   return KSG_OK;
 }
 
+int ksg_debug_same_pods(const ksg_ctx* ctx, uint64_t* taken, uint64_t* not_taken) {
+  if (!ctx || !taken || !not_taken) return KSG_EINVAL;
+  *taken = ctx->engine->same_pods_;
+  *not_taken = ctx->engine->not_same_pods_;
+  return KSG_OK;
+}
+
+int ksg_debug_sched_same(ksg_ctx* ctx, int32_t handle_a, int32_t handle_b) {
+  if (!ctx) return KSG_EINVAL;
+  try {
+    ksg::Engine* e = ctx->engine.get();
+    auto a = e->queue.find(handle_a), b = e->queue.find(handle_b);
+    if (a == e->queue.end() || b == e->queue.end()) return KSG_EINVAL;
+    ksg::CompiledPod ca, cb;
+    int rc = e->compile(a->second, ksg::Engine::CYCLE, -1, true, false, &ca);
+    if (rc == KSG_OK) {
+      rc = e->compile(b->second, ksg::Engine::CYCLE, -1, true, false, &cb);
+      e->c->pod_table_drop(ca.slot);
+      if (rc == KSG_OK) e->c->pod_table_drop(cb.slot);
+    }
+    if (rc != KSG_OK) return rc;
+    return ksg::Engine::sched_same(ca, cb) ? 1 : 0;
+  } catch (...) {
+    return KSG_EINVAL;
+  }
+}
+
 int ksg_debug_log_table(double* out, int32_t n) {
   if (!out || n < 0) return KSG_EINVAL;
   for (int32_t k = 0; k < n; ++k) out[k] = ksg::go_log((double)k);  // as Cluster::upload_pod_table builds it

@@ -69,6 +69,8 @@ hipError_t launch_sched_loop(const MirrorView& m, const BatchView& b, const Loop
                              hipEvent_t t0, hipEvent_t t1, int unit);
 hipError_t launch_agg_loop(const MirrorView& m, const BatchView& b, const AggView& av, hipStream_t s, hipEvent_t t0,
                            hipEvent_t t1);
+hipError_t launch_sched_same(const MirrorView& m, const BatchView& b, const LoopView& lv, hipStream_t s, hipEvent_t t0,
+                             hipEvent_t t1);
 hipError_t launch_put_group_arg(const LoopGroupArg& a, LoopGroupArg* dst, hipStream_t s);
 hipError_t launch_put_group_arg(const AggGroupArg& a, AggGroupArg* dst, hipStream_t s);
 hipError_t launch_sched_loop_group(const LoopGroupArg* ga, int world, int nwg, hipStream_t s, hipEvent_t t0,
@@ -1558,6 +1560,47 @@ static bool agg_same(const std::vector<uint8_t>& a, const std::vector<uint8_t>& 
 
 static bool agg_same(const CompiledPod& a, const CompiledPod& b) { return !a.error && !b.error && agg_same(a.blob, b.blob); }
 
+// k_sched_same.  A pod it can take: the default-plugin shape with zero raw scores, scoring,
+// assumed on the device, over the whole snapshot, and whose AssumePod writes nothing a Filter of the next pod reads
+// beyond the core columns (no host port, no scalar resource).
+bool Engine::same_eligible(const CompiledPod& p) {
+  if (p.error || p.blob.size() < sizeof(PodDesc) || p.blob.size() > (size_t)kBlobLds || p.blob.size() % 16 != 0) return false;
+  PodDesc d;
+  std::memcpy(&d, p.blob.data(), sizeof(PodDesc));
+  constexpr uint32_t need = DF_FAST | DF_RAW0 | DF_ASSUME;
+  constexpr uint32_t never = DF_ROTDEV | DF_SAMPLE | DF_SUBSET | DF_EARLY | DF_DIAG | DF_NOM_TOPO | DF_PREFILTER_REJECT |
+                             DF_SCORE_ERROR | DF_EVAL_OUT | DF_ALL_FEASIBLE | DF_NODE_LIST | DF_NO_SCORE | DF_AGGREGATE;
+  return (d.flags & need) == need && !(d.flags & never) && d.n_pod_ports == 0 && d.n_a_scalar == 0 && d.node_name == -1;
+}
+// Pod b may follow pod a in one run: both eligible and one program, byte for byte, but for the fields neither the
+// evaluation nor the selection of the run reads from the shared copy -- the pod-table slot and the rotation start
+// (the kernel takes each pod's own), the previous launched pod (DF_ROTDEV only) and k_agg_loop's DF_AGG_SAME.
+// (the programs alone: byte ranges between the masked fields, no copies -- this runs once per pod of every loop run)
+static bool same_programs(const CompiledPod& a, const CompiledPod& b) {
+  if (a.error || b.error || a.blob.size() != b.blob.size() || a.blob.size() < sizeof(PodDesc)) return false;
+  const uint8_t *x = a.blob.data(), *y = b.blob.data();
+  uint32_t fa, fb;
+  std::memcpy(&fa, x + offsetof(PodDesc, flags), 4);
+  std::memcpy(&fb, y + offsetof(PodDesc, flags), 4);
+  if ((fa & ~DF_AGG_SAME) != (fb & ~DF_AGG_SAME)) return false;
+  // the masked 4-byte fields, ascending; everything between them, and the payload, must be equal
+  static_assert(offsetof(PodDesc, flags) < offsetof(PodDesc, rot_start) && offsetof(PodDesc, rot_start) < offsetof(PodDesc, slot) &&
+                    offsetof(PodDesc, slot) < offsetof(PodDesc, prev_pod),
+                "same_programs: the masked fields in layout order");
+  const size_t cutp[] = {offsetof(PodDesc, flags), offsetof(PodDesc, rot_start), offsetof(PodDesc, slot),
+                         offsetof(PodDesc, prev_pod)};
+  size_t from = 0;
+  for (size_t o : cutp) {
+    if (std::memcmp(x + from, y + from, o - from) != 0) return false;
+    from = o + 4;
+  }
+  return std::memcmp(x + from, y + from, a.blob.size() - from) == 0;
+}
+bool Engine::sched_same(const CompiledPod& a, const CompiledPod& b) {
+  // (b is eligible when a is and the programs match: every field the eligibility reads is compared)
+  return same_eligible(a) && same_programs(a, b);
+}
+
 // The resident k_agg_loop's RING_TERMS doorbell (desc.h): pod b (program nb, entry ne) is pod a's but for its slot,
 // rotation, DF_AGG_SAME, label-pool offset -- as RING_SAME -- and its own affinity terms' table indices and the
 // term-pool offset of their words.  The loop's patch is replayed on a's bytes; true (and the patch words) only when
@@ -2619,6 +2662,20 @@ int Engine::run_batch(const std::vector<const PodSpec*>& pods, const std::vector
     htrace("staged", i);
     return r2;
   };
+  // k_sched_same's launches: unsharded batch runs without a nominee table, a diagnosis, stamps or a forced
+  // give-up, over at most kSameMaxNodes nodes
+  const bool same_ok = use_loop && c->cfg.loop_same_template && W == 1 && !comm && m.nom == nullptr && !diag &&
+                       !c->cfg.loop_stamps && c->cfg.debug_give_up_at < 0 && m.n <= kSameMaxNodes;
+  int ss_at = -1, ss_len = 0;  // the last stretch measured
+  // pods [a, a + result) are eligible and of one template (within the chunk and a launch's pod limit)
+  auto same_stretch = [&](int a, int cut) -> int {
+    if (a == ss_at) return ss_len;
+    int e = a;
+    if (same_eligible(cp[a]))
+      for (e = a + 1; e < n && e < cut && e - a < kLoopMaxPods && same_programs(cp[e - 1], cp[e]);) ++e;
+    ss_at = a;
+    return ss_len = e - a;
+  };
   for (int i = 0; i < n && (!comm || dx);) {
     if (i > 0 && std::binary_search(bnd.begin(), bnd.end(), i) && (chunks.empty() || chunks.back().b < i)) {
       if (i >= compiled && (rc = next_chunk(i))) return rc;  // its H2D does not wait for chunk k
@@ -2632,8 +2689,15 @@ int Engine::run_batch(const std::vector<const PodSpec*>& pods, const std::vector
       int j = i;
       double rb = 0;
       const int cut = chunk_end(i);
+      // k_sched_same: the loop run is cut into maximal stretches of eligible pods of one template; a stretch of at
+      // least loopSameMinRun pods is a run of its own and goes to the one-workgroup kernel, the rest to k_sched_loop
+      const bool same_run = same_ok && same_stretch(i, cut) >= c->cfg.loop_same_min_run;
+      const int same_end = same_run ? i + same_stretch(i, cut) : -1;
       while (j < n && j < cut && j - i < kLoopMaxPods && loop_ok(cp[j])) {
+        if (same_run ? j >= same_end : (same_ok && j > i && same_stretch(j, cut) >= c->cfg.loop_same_min_run)) break;
         const PodDesc& hd = *reinterpret_cast<const PodDesc*>(cp[j++].blob.data());
+        if (same_run) ++same_pods_;
+        else ++not_same_pods_;
         count_lean(hd);
         rb += algo_bytes(hd) * (comm && m.n > 0 ? std::min(1.0, (double)snblk * kBlock / (double)m.n) : 1.0);
       }
@@ -2678,6 +2742,8 @@ int Engine::run_batch(const std::vector<const PodSpec*>& pods, const std::vector
         req.t0 = t0;
         req.t1 = t1;
         if ((rc = group_launch(&req, false, GS, unit))) return rc;
+      } else if (same_run) {
+        HIPCHK(launch_sched_same(m, bv, lv, s, t0, t1));
       } else {
         HIPCHK(launch_sched_loop(m, bv, lv, s, t0, t1, unit));
       }

@@ -241,6 +241,10 @@ struct Config {
   // k_sched_loop: the lean path for DF_RAW0 pods ("loopLeanSelect": true / false, or a mask of its parts for
   // measurements: desc.h kLeanA | kLeanP2 | kLeanP1)
   int loop_lean_select = kLeanAll;
+  // k_sched_same: stretches of at least loop_same_min_run eligible same-template pods of a k_sched_loop run go to
+  // the one-workgroup kernel ("loopSameTemplate", "loopSameMinRun"; false: k_sched_loop as before)
+  bool loop_same_template = true;
+  int loop_same_min_run = 16;
   // k_agg_loop: batch runs of sampled pods (DF_ROTDEV: percentageOfNodesToScore < 100, a no-score profile, a
   // nominated pod in the batch) through its sampling instances ("aggLoopSampled"; false: the launch path, as before)
   bool agg_loop_sampled = true;
@@ -629,6 +633,11 @@ class Engine {
     if (!c->cfg.loop_lean_select) return;
     ++((hd.flags & (DF_RAW0 | DF_NO_SCORE)) == DF_RAW0 ? lean_pods_ : general_pods_);
   }
+  // pods of k_sched_loop's runs that k_sched_same ran, and that k_sched_loop ran (ksg_debug_same_pods)
+  uint64_t same_pods_ = 0, not_same_pods_ = 0;
+  // a pod k_sched_same can take, and whether pod b may follow pod a in one of its runs (engine.cpp)
+  static bool same_eligible(const CompiledPod& p);
+  static bool sched_same(const CompiledPod& a, const CompiledPod& b);
   int run_plugin(const PodSpec& p, Mode mode, int plugin, const uint8_t* nodes, int32_t* code, uint8_t* codes,
                  uint32_t* reasons, int64_t* raw, int64_t* norm);
   // DefaultPreemption's PostFilter for a pod that failed its cycle (preempt.cpp)

@@ -140,6 +140,26 @@ class Scheduler(Backend):
         self._chk(fn(self.ctx, C.byref(a), C.byref(b)), "lean_pods")
         return a.value, b.value
 
+    def same_pods(self):
+        """(taken, not_taken): the pods of k_sched_loop's runs so far that k_sched_same ran, and that k_sched_loop
+        ran (ksg_debug_same_pods; bound on first use, as lean_pods)."""
+        fn = self.lib.ksg_debug_same_pods
+        fn.restype = C.c_int
+        fn.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+        a, b = C.c_uint64(), C.c_uint64()
+        self._chk(fn(self.ctx, C.byref(a), C.byref(b)), "same_pods")
+        return a.value, b.value
+
+    def sched_same(self, handle_a, handle_b):
+        """Whether pod b may follow pod a in a k_sched_same run (ksg_debug_sched_same; schedules nothing)."""
+        fn = self.lib.ksg_debug_sched_same
+        fn.restype = C.c_int
+        fn.argtypes = [C.c_void_p, C.c_int32, C.c_int32]
+        rc = fn(self.ctx, handle_a, handle_b)
+        if rc < 0:
+            self._chk(rc, "sched_same")
+        return rc == 1
+
     def relayouts(self):
         """(full mirror rebuilds, gather re-layouts) so far (ksg_debug_relayouts)."""
         f, g = C.c_uint64(), C.c_uint64()
