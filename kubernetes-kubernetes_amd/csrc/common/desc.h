@@ -739,7 +739,11 @@ constexpr int kSameGroups = kSameMaxNodes / 64;                       // 64-node
 // LDS: the program, per node the post-assume fixed score (8 B) and a pending byte, per group the two ballots,
 // per pod its slot, rotation start and decided {key, node, F}
 constexpr int kSameLdsBytes = kBlobLds + kSameMaxNodes * (8 + 1) + kSameGroups * 16 + kLoopMaxPods * (4 + 4 + 16) + 256;
-static_assert(kSameLdsBytes <= 160 * 1024, "k_sched_same: one workgroup's LDS (160 KiB per CU on gfx950)");
+// the sampled instance (DF_ROTDEV runs, k_sched_same<1>) adds per pod its rotation start and processedNodes, and the
+// scan waves' end-node words
+constexpr int kSameSampledLdsBytes = kSameLdsBytes + kLoopMaxPods * (4 + 4) + 64;
+static_assert(kSameLdsBytes <= 160 * 1024 && kSameSampledLdsBytes <= 160 * 1024,
+              "k_sched_same: one workgroup's LDS (160 KiB per CU on gfx950)");
 static_assert(kSameGroups <= 128, "k_sched_same: the group prefix scan holds two groups per lane");
 static_assert(kSameMaxNodes >= 5000, "k_sched_same: the flagship workload's nodes fit");
 

@@ -22,6 +22,7 @@
 #include <hip/hip_runtime.h>
 
 #include <atomic>
+#include <type_traits>
 
 #include "device.hpp"
 
@@ -7428,6 +7429,14 @@ struct SameLds {
   uint8_t pend[kSameMaxNodes];                     // 1: the node's post evaluation is on its way
 };
 static_assert(sizeof(SameLds) <= (size_t)kSameLdsBytes, "k_sched_same: LDS layout (desc.h kSameLdsBytes)");
+// the sampled instance (k_sched_same<1>, DF_ROTDEV runs): per pod its rotation start and processedNodes for the
+// committing thread, and per pod parity the cut's end node as its scan wave found it
+struct SameLdsSampled : SameLds {
+  uint32_t res_rot[kLoopMaxPods];                  // pod q decided: its nextStartNodeIndex,
+  uint32_t res_proc[kLoopMaxPods];                 // its processedNodes (the next pod's start follows from both)
+  uint32_t wend[2][kSameScanWaves];                // [pod parity] the (K+1)-th feasible node, 0xffffffff: not mine
+};
+static_assert(sizeof(SameLdsSampled) <= (size_t)kSameSampledLdsBytes, "k_sched_same<1>: LDS layout (desc.h kSameSampledLdsBytes)");
 
 // bounded wait for an LDS word to reach `want` (~2 s of the 100 MHz clock); false: gave up or another wave did
 __device__ __forceinline__ bool same_wait(SameLds& L, const uint32_t* word, uint32_t want, uint32_t* fail, int q, int what) {
@@ -7484,14 +7493,18 @@ __device__ __forceinline__ NodeEval same_eval(const MirrorView& m, NodeCore c, i
   return eval_core_fast<false>(m, c, bal2(c.rcpu, c.acpu, c.rmem, c.amem), pf, base, d, i);
 }
 
-// (a template: its instance is emitted behind every plain kernel, with the other loops' instances -- see k_text_phase_pad)
-template <int kUnused>
+// (a template: its instances are emitted behind every plain kernel, with the other loops' instances -- see k_text_phase_pad)
+// kSampled: the run's pods carry DF_ROTDEV -- nextStartNodeIndex lives on the device and moves with every cut, so the
+// scan lanes keep {total, global feasible index} per node and form each pod's positions, cut and keys in registers
+// (schedule_one.go:686-687, 778-782, 809-824, as k_sched_loop's selection wave does them).  0: the instance of the
+// runs whose rotation start the host stamped into every program, unchanged.
+template <int kSampled>
 __global__ __launch_bounds__(kSameThreads) void k_sched_same(MirrorView m_, BatchView b_, LoopView lv_) {
   const LoopGroupArg& ka = *(const LoopGroupArg*)__builtin_amdgcn_kernarg_segment_ptr();  // (k_sched_loop)
   const MirrorView& m = ka.m;
   const BatchView& b = ka.b;
   const LoopView& lv = ka.lv;
-  __shared__ SameLds L;
+  __shared__ std::conditional_t<kSampled != 0, SameLdsSampled, SameLds> L;
   constexpr int kScanThreads = kSameScanWaves * 64;
   const int tid = (int)threadIdx.x, lane = tid & 63;
   const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -7527,10 +7540,14 @@ __global__ __launch_bounds__(kSameThreads) void k_sched_same(MirrorView m_, Batc
 
   // ---- fill: scan thread t evaluates its nodes as they are, commit thread t the same nodes with one pod assumed
   unsigned long long key[kSameSlots];  // scan lanes: pack_best(total, position) of my nodes, 0: infeasible
+  // kSampled, instead: my nodes' totals (< 2^19, host-checked) and their global feasible indices -- a node keeps
+  // its total while the cut's window leaves it outside
+  [[maybe_unused]] uint32_t tot[kSameSlots], gi[kSameSlots];
   const int st = scan ? tid : tid - kScanThreads;
 #pragma unroll
   for (int j = 0; j < kSameSlots; ++j) {
     key[j] = 0ull;
+    if constexpr (kSampled) tot[j] = gi[j] = 0u;
     const int g0 = j * kScanThreads + (st & ~63);  // my group's first node (uniform)
     if (g0 < n) {
       const int i = g0 + lane;
@@ -7538,7 +7555,8 @@ __global__ __launch_bounds__(kSameThreads) void k_sched_same(MirrorView m_, Batc
       if (i < n) ne = same_eval(m, load_core<false>(m, i), scan ? 0 : 1, pf, base, d, i);
       const unsigned long long bl = __ballot(ne.st == 0);
       if (scan) {
-        key[j] = ne.st == 0 ? pack_best(ne.fixed + add, 0u) : 0ull;  // (the position: rebuild below)
+        if constexpr (kSampled) tot[j] = ne.st == 0 ? (uint32_t)(ne.fixed + add) : 0u;
+        else key[j] = ne.st == 0 ? pack_best(ne.fixed + add, 0u) : 0ull;  // (the position: rebuild below)
         if (lane == 0) L.ball0[g0 >> 6] = bl;
       } else {
         if (i < n) L.fx1[i] = ne.fixed;
@@ -7562,6 +7580,13 @@ __global__ __launch_bounds__(kSameThreads) void k_sched_same(MirrorView m_, Batc
         const uint32_t F = L.res_F[q];
         const unsigned long long best = L.res_key[q];
         const int ipa = (int)b.stats[pod].ipa_any;
+        if constexpr (kSampled) {  // the rotation bookkeeping commit_result reports (k_sched_loop's rot_stats)
+          PodStats* ps = b.stats + pod;
+          const uint32_t rot = L.res_rot[q], proc = L.res_proc[q];
+          ps->rot = rot;
+          ps->processed = proc;
+          ps->rot_out = m.n > 0 ? (uint32_t)(((uint64_t)rot + proc) % (uint64_t)m.n) : 0u;
+        }
         if (node < 0) {
           commit_result(m, b, base, d, b.stats + pod, pod, 0u, -1, best, nullptr, ipa);
         } else {
@@ -7626,6 +7651,149 @@ __global__ __launch_bounds__(kSameThreads) void k_sched_same(MirrorView m_, Batc
     }
     psb_cur = psb;
   };
+  if constexpr (kSampled) {
+    // ======== the sampled form.  Per pod (uniform): rot = its nextStartNodeIndex, psb, cut = F > K, the kept window
+    // (positions < K) and gK = the global feasible index of the (K+1)-th node in rotated order.  Per lane: a node's
+    // position, whether the window keeps it and its key, from {tot, gi} -- nothing is re-read from LDS; gi changes only
+    // when a ballot flips.  While a cut is active every pod moves every position, so every pod forms its wave's best
+    // anew; without one the rotation stands still and the cached best holds as in the other instance.
+    const uint32_t N = (uint32_t)n;
+    const uint32_t K = (uint32_t)__builtin_amdgcn_readfirstlane(d.num_to_find);
+    uint32_t feas = 0;  // bit j: my node of slot j is feasible as it is
+    auto reindex = [&]() __attribute__((always_inline)) {
+      const unsigned long long lt = (1ull << lane) - 1ull;
+      feas = 0;
+#pragma unroll
+      for (int j = 0; j < kSameSlots; ++j) {
+        const int grp = j * kSameScanWaves + wv;
+        const unsigned long long bl = L.ball0[grp];
+        gi[j] = before(grp) + (uint32_t)__popcll(bl & lt);
+        feas |= (uint32_t)((bl >> lane) & 1ull) << j;
+      }
+    };
+    auto mod_n = [&](uint64_t x) __attribute__((always_inline)) -> uint32_t {  // x % N, N > 0 (x < 2 N but for a stale start)
+      return x < N ? (uint32_t)x : x < 2ull * N ? (uint32_t)(x - N) : (uint32_t)(x % (uint64_t)N);
+    };
+    scan_groups();
+    reindex();
+    // the previous launched pod's nextStartNodeIndex, or the host's (the first pod's own descriptor is the shared copy)
+    uint32_t rot = (uint32_t)__builtin_amdgcn_readfirstlane(
+        (int)(d.prev_pod < 0 ? b.stats[lv.first_pod].rot_in : b.stats[d.prev_pod].rot_out));
+    bool dirty = true;
+    unsigned long long wk = 0;  // my wave's best key, its node, that node's post feasibility, my wave's end node
+    int wn = -1;
+    uint32_t wpb = 0, wen = 0xffffffffu;
+    uint32_t nflip = 0;
+    for (int q = 0; q < npods; ++q) {
+      const int par = q & 1;
+      const uint32_t psb = psb_of((int)(rot < (uint32_t)kSameMaxNodes ? rot : (uint32_t)kSameMaxNodes));
+      const bool cut = F > K;
+      const uint32_t keep = cut ? K : 0xffffffffu;
+      const uint32_t gK = cut ? (psb + K >= F ? psb + K - F : psb + K) : 0xffffffffu;  // psb <= F, K < F
+      if (dirty || cut) {
+        // (the packed 64-bit key per slot, as phase2_lean forms it: comparing its two halves as 32-bit words instead
+        // measured 0.17 us per pod slower -- profiles/same_sampled_bench_ab.txt)
+        unsigned long long k = 0;
+        int kj = 0, ej = -1;
+#pragma unroll
+        for (int j = 0; j < kSameSlots; ++j) {
+          const bool f = ((feas >> j) & 1u) != 0;
+          const uint32_t g = gi[j];
+          const uint32_t pos = g >= psb ? g - psb : g + F - psb;
+          const unsigned long long kv = f && pos < keep ? pack_best((int64_t)tot[j], pos) : 0ull;
+          ej = f && g == gK ? j : ej;
+          kj = kv > k ? j : kj;
+          k = kv > k ? kv : k;
+        }
+        wk = wave_max_u64(k);
+        const unsigned long long hold = __ballot(k == wk && k != 0ull);  // keys are unique
+        wn = -1;
+        wpb = 0;
+        if (hold) {
+          const int hl = (int)__builtin_ctzll(hold);
+          wn = __builtin_amdgcn_readlane(kj, hl) * kScanThreads + wv * 64 + hl;
+          if (!same_wait_pend(L, wn, lv.fail, q)) return;
+          wpb = (uint32_t)((L.ball1[wn >> 6] >> (wn & 63)) & 1ull);
+        }
+        const unsigned long long eh = __ballot(ej >= 0);  // at most one node of the run has g == gK
+        wen = 0xffffffffu;
+        if (eh) {
+          const int el = (int)__builtin_ctzll(eh);
+          wen = (uint32_t)(__builtin_amdgcn_readlane(ej, el) * kScanThreads + wv * 64 + el);
+        }
+        dirty = false;
+      }
+      if (lane == 0) {
+        L.wkey[par][wv] = wk;
+        L.wnode[par][wv] = (uint32_t)wn | (wpb << 31);
+        L.wend[par][wv] = wen;
+        __hip_atomic_fetch_add(&L.arrive, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
+      }
+      if (!same_wait(L, &L.arrive, (uint32_t)kSameScanWaves * (uint32_t)(q + 1), lv.fail, q, 0)) return;
+      // the run's winner and the cut's end node: every wave reads the same words, so all decide alike
+      unsigned long long gk = 0;
+      uint32_t gn = 0xffffffffu, en = 0xffffffffu;
+#pragma unroll
+      for (int v = 0; v < kSameScanWaves; ++v) {
+        const unsigned long long kv = L.wkey[par][v];
+        const uint32_t nv = L.wnode[par][v], ev = L.wend[par][v];
+        gn = kv > gk ? nv : gn;
+        gk = kv > gk ? kv : gk;
+        en = ev < en ? ev : en;
+      }
+      gk = ((unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(gk >> 32)) << 32) |
+           (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)gk);
+      gn = (uint32_t)__builtin_amdgcn_readfirstlane((int)gn);
+      en = (uint32_t)__builtin_amdgcn_readfirstlane((int)en);
+      // processedNodes: with a cut the nodes before the (K+1)-th feasible one in rotated order (its rotated position:
+      // K + the failures before it), else every node; the next pod's start
+      const uint32_t proc = cut && en < N ? mod_n((uint64_t)((int64_t)en - (int64_t)rot + (int64_t)N)) : N;
+      const uint32_t rot_next = N > 0 ? mod_n((uint64_t)rot + proc) : 0u;
+      if (gk == 0ull) {  // no feasible node: nothing changes but the bookkeeping
+        if (wv == 0 && lane == 0) {
+          L.res_key[q] = 0ull;
+          L.res_node[q] = -1;
+          L.res_F[q] = 0u;
+          L.res_rot[q] = rot;
+          L.res_proc[q] = proc;
+          __hip_atomic_store(&L.done, (uint32_t)(q + 1), __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
+        }
+        rot = rot_next;
+        continue;
+      }
+      const int win = (int)(gn & 0x7fffffffu);
+      const bool stays = (gn >> 31) != 0u;  // the winner is still feasible with this pod on it
+      const int wslot = win % kScanThreads;
+      if ((wslot >> 6) == wv) {  // mine: its total := its post evaluation
+        const int wj = win / kScanThreads;
+        const uint32_t nt = stays ? (uint32_t)(L.fx1[win] + add) : 0u;
+        const bool me = lane == (wslot & 63);
+#pragma unroll
+        for (int j = 0; j < kSameSlots; ++j) tot[j] = me && j == wj ? nt : tot[j];
+        if (me) {
+          if (!stays) L.ball0[win >> 6] &= ~(1ull << (win & 63));
+          L.pend[win] = 1;
+          L.res_key[q] = gk;
+          L.res_node[q] = win;
+          L.res_F[q] = cut ? K : F;  // the feasible list's length
+          L.res_rot[q] = rot;
+          L.res_proc[q] = proc;
+          __hip_atomic_store(&L.done, (uint32_t)(q + 1), __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
+        }
+        dirty = true;
+      }
+      if (!stays) {  // a ballot changed: once its owner has stored it, every wave takes its nodes' indices again
+        ++nflip;
+        if (lane == 0) __hip_atomic_fetch_add(&L.arrive2, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
+        if (!same_wait(L, &L.arrive2, (uint32_t)kSameScanWaves * nflip, lv.fail, q, 1)) return;
+        scan_groups();
+        reindex();
+        dirty = true;
+      }
+      rot = rot_next;
+    }
+    return;
+  }
   scan_groups();
   rebuild(psb_of(npods > 0 ? L.rot[0] : 0));
   bool dirty = true;         // my wave's best must be formed again
@@ -7720,11 +7888,13 @@ __global__ __launch_bounds__(kSameThreads) void k_sched_same(MirrorView m_, Batc
   }
 }
 hipError_t launch_sched_same(const MirrorView& m, const BatchView& b, const LoopView& lv, hipStream_t s, hipEvent_t t0,
-                             hipEvent_t t1) {
+                             hipEvent_t t1, bool sampled) {
   if (lv.npods < 1 || lv.npods > kLoopMaxPods || m.n > kSameMaxNodes || m.nom != nullptr || lv.ring != nullptr)
     return hipErrorInvalidValue;
-  if (t0) hipExtLaunchKernelGGL(k_sched_same<0>, dim3(1), dim3(kSameThreads), 0, s, t0, t1, 0, m, b, lv);
-  else hipLaunchKernelGGL(k_sched_same<0>, dim3(1), dim3(kSameThreads), 0, s, m, b, lv);
+  // sampled: the run's pods carry DF_ROTDEV (per batch, so all of them or none)
+  auto* fn = sampled ? k_sched_same<1> : k_sched_same<0>;
+  if (t0) hipExtLaunchKernelGGL(fn, dim3(1), dim3(kSameThreads), 0, s, t0, t1, 0, m, b, lv);
+  else hipLaunchKernelGGL(fn, dim3(1), dim3(kSameThreads), 0, s, m, b, lv);
   return hipGetLastError();
 }
 

@@ -625,7 +625,7 @@ int ksg_debug_sched_same(ksg_ctx* ctx, int32_t handle_a, int32_t handle_b) {
       if (rc == KSG_OK) e->c->pod_table_drop(cb.slot);
     }
     if (rc != KSG_OK) return rc;
-    return ksg::Engine::sched_same(ca, cb) ? 1 : 0;
+    return ksg::Engine::sched_same(ca, cb, e->c->cfg.loop_same_sampled) ? 1 : 0;
   } catch (...) {
     return KSG_EINVAL;
   }

@@ -70,7 +70,7 @@ hipError_t launch_sched_loop(const MirrorView& m, const BatchView& b, const Loop
 hipError_t launch_agg_loop(const MirrorView& m, const BatchView& b, const AggView& av, hipStream_t s, hipEvent_t t0,
                            hipEvent_t t1);
 hipError_t launch_sched_same(const MirrorView& m, const BatchView& b, const LoopView& lv, hipStream_t s, hipEvent_t t0,
-                             hipEvent_t t1);
+                             hipEvent_t t1, bool sampled);
 hipError_t launch_put_group_arg(const LoopGroupArg& a, LoopGroupArg* dst, hipStream_t s);
 hipError_t launch_put_group_arg(const AggGroupArg& a, AggGroupArg* dst, hipStream_t s);
 hipError_t launch_sched_loop_group(const LoopGroupArg* ga, int world, int nwg, hipStream_t s, hipEvent_t t0,
@@ -1562,15 +1562,18 @@ static bool agg_same(const CompiledPod& a, const CompiledPod& b) { return !a.err
 
 // k_sched_same.  A pod it can take: the default-plugin shape with zero raw scores, scoring,
 // assumed on the device, over the whole snapshot, and whose AssumePod writes nothing a Filter of the next pod reads
-// beyond the core columns (no host port, no scalar resource).
-bool Engine::same_eligible(const CompiledPod& p) {
+// beyond the core columns (no host port, no scalar resource).  sampled ("loopSameSampled"): also the pods whose
+// nextStartNodeIndex lives on the device (DF_ROTDEV), with or without a cut (DF_SAMPLE) -- the kernel's sampled instance.
+bool Engine::same_eligible(const CompiledPod& p, bool sampled) {
   if (p.error || p.blob.size() < sizeof(PodDesc) || p.blob.size() > (size_t)kBlobLds || p.blob.size() % 16 != 0) return false;
   PodDesc d;
   std::memcpy(&d, p.blob.data(), sizeof(PodDesc));
   constexpr uint32_t need = DF_FAST | DF_RAW0 | DF_ASSUME;
-  constexpr uint32_t never = DF_ROTDEV | DF_SAMPLE | DF_SUBSET | DF_EARLY | DF_DIAG | DF_NOM_TOPO | DF_PREFILTER_REJECT |
+  constexpr uint32_t rotating = DF_ROTDEV | DF_SAMPLE;
+  constexpr uint32_t never = DF_SUBSET | DF_EARLY | DF_DIAG | DF_NOM_TOPO | DF_PREFILTER_REJECT |
                              DF_SCORE_ERROR | DF_EVAL_OUT | DF_ALL_FEASIBLE | DF_NODE_LIST | DF_NO_SCORE | DF_AGGREGATE;
-  return (d.flags & need) == need && !(d.flags & never) && d.n_pod_ports == 0 && d.n_a_scalar == 0 && d.node_name == -1;
+  return (d.flags & need) == need && !(d.flags & never) && (sampled || !(d.flags & rotating)) && d.n_pod_ports == 0 &&
+         d.n_a_scalar == 0 && d.node_name == -1;
 }
 // Pod b may follow pod a in one run: both eligible and one program, byte for byte, but for the fields neither the
 // evaluation nor the selection of the run reads from the shared copy -- the pod-table slot and the rotation start
@@ -1596,9 +1599,9 @@ static bool same_programs(const CompiledPod& a, const CompiledPod& b) {
   }
   return std::memcmp(x + from, y + from, a.blob.size() - from) == 0;
 }
-bool Engine::sched_same(const CompiledPod& a, const CompiledPod& b) {
+bool Engine::sched_same(const CompiledPod& a, const CompiledPod& b, bool sampled) {
   // (b is eligible when a is and the programs match: every field the eligibility reads is compared)
-  return same_eligible(a) && same_programs(a, b);
+  return same_eligible(a, sampled) && same_programs(a, b);
 }
 
 // The resident k_agg_loop's RING_TERMS doorbell (desc.h): pod b (program nb, entry ne) is pod a's but for its slot,
@@ -2671,7 +2674,7 @@ int Engine::run_batch(const std::vector<const PodSpec*>& pods, const std::vector
   auto same_stretch = [&](int a, int cut) -> int {
     if (a == ss_at) return ss_len;
     int e = a;
-    if (same_eligible(cp[a]))
+    if (same_eligible(cp[a], c->cfg.loop_same_sampled))
       for (e = a + 1; e < n && e < cut && e - a < kLoopMaxPods && same_programs(cp[e - 1], cp[e]);) ++e;
     ss_at = a;
     return ss_len = e - a;
@@ -2743,7 +2746,9 @@ int Engine::run_batch(const std::vector<const PodSpec*>& pods, const std::vector
         req.t1 = t1;
         if ((rc = group_launch(&req, false, GS, unit))) return rc;
       } else if (same_run) {
-        HIPCHK(launch_sched_same(m, bv, lv, s, t0, t1));
+        // (rotdev() is per batch: the run's pods all carry DF_ROTDEV, or none does)
+        HIPCHK(launch_sched_same(m, bv, lv, s, t0, t1,
+                                 (reinterpret_cast<const PodDesc*>(cp[i].blob.data())->flags & DF_ROTDEV) != 0));
       } else {
         HIPCHK(launch_sched_loop(m, bv, lv, s, t0, t1, unit));
       }

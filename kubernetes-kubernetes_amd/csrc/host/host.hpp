@@ -245,6 +245,11 @@ struct Config {
   // the one-workgroup kernel ("loopSameTemplate", "loopSameMinRun"; false: k_sched_loop as before)
   bool loop_same_template = true;
   int loop_same_min_run = 16;
+  // k_sched_same's sampled instance: such stretches also when nextStartNodeIndex lives on the device (DF_ROTDEV:
+  // percentageOfNodesToScore < 100 -- 0, upstream's adaptive default, included -- or a nominated pod in the batch),
+  // with the cut and the rotation carried inside the kernel ("loopSameSampled"; false: those pods stay in
+  // k_sched_loop, as before)
+  bool loop_same_sampled = true;
   // k_agg_loop: batch runs of sampled pods (DF_ROTDEV: percentageOfNodesToScore < 100, a no-score profile, a
   // nominated pod in the batch) through its sampling instances ("aggLoopSampled"; false: the launch path, as before)
   bool agg_loop_sampled = true;
@@ -636,8 +641,9 @@ class Engine {
   // pods of k_sched_loop's runs that k_sched_same ran, and that k_sched_loop ran (ksg_debug_same_pods)
   uint64_t same_pods_ = 0, not_same_pods_ = 0;
   // a pod k_sched_same can take, and whether pod b may follow pod a in one of its runs (engine.cpp)
-  static bool same_eligible(const CompiledPod& p);
-  static bool sched_same(const CompiledPod& a, const CompiledPod& b);
+  // (sampled: config loop_same_sampled -- pods with a device-resident nextStartNodeIndex too)
+  static bool same_eligible(const CompiledPod& p, bool sampled);
+  static bool sched_same(const CompiledPod& a, const CompiledPod& b, bool sampled);
   int run_plugin(const PodSpec& p, Mode mode, int plugin, const uint8_t* nodes, int32_t* code, uint8_t* codes,
                  uint32_t* reasons, int64_t* raw, int64_t* norm);
   // DefaultPreemption's PostFilter for a pod that failed its cycle (preempt.cpp)

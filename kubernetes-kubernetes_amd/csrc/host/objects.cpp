@@ -925,6 +925,7 @@ bool decode_config(const char* p, size_t n, Config* c, std::string* err) {
       c->loop_lean_select = ls->type == JVal::BOOL ? (ls->b ? kLeanAll : 0) : ((int)d.num(r, "loopLeanSelect", kLeanAll) & kLeanAll);
     if (const JVal* st = d.get(r, "loopSameTemplate")) c->loop_same_template = !(st->type == JVal::BOOL && !st->b);
     c->loop_same_min_run = std::max(1, (int)d.num(r, "loopSameMinRun", c->loop_same_min_run));
+    if (const JVal* ss = d.get(r, "loopSameSampled")) c->loop_same_sampled = !(ss->type == JVal::BOOL && !ss->b);
     if (const JVal* as = d.get(r, "aggLoopSampled")) c->agg_loop_sampled = !(as->type == JVal::BOOL && !as->b);
     if (const JVal* ra = d.get(r, "residentAhead")) c->resident_ahead = !(ra->type == JVal::BOOL && !ra->b);
     c->first_chunk = std::max(8, std::min(256, (int)d.num(r, "pipelineFirstChunk", 32)));
