@@ -444,8 +444,10 @@ int ksg_debug_lean_pods(const ksg_ctx *ctx, uint64_t *lean, uint64_t *general);
 /* k_sched_same (config "loopSameTemplate", default true; "loopSameMinRun"): of the pods of
  * k_sched_loop's runs since the context was created, those that went to k_sched_same -- stretches of at least
  * loopSameMinRun eligible pods stamped from one template, on an unsharded context of at most 8192 nodes without a
- * nominee table, a diagnosis or loopStamps -- (*taken) and those k_sched_loop ran (*not_taken).  Counted on the
- * host. */
+ * nominee table or loopStamps -- (*taken) and those k_sched_loop ran (*not_taken).  Counted on the host.
+ * A diagnosed batch (ksg_schedule_batch_diag) is routed the same way (config "loopSameDiag", default true;
+ * DESIGN.md §4.11): k_same_diag behind each run reduces the run's FitErrors into their rows.  false: no pod of a
+ * diagnosed batch is taken, as before the key existed; results and diagnoses are the same either way. */
 int ksg_debug_same_pods(const ksg_ctx *ctx, uint64_t *taken, uint64_t *not_taken);
 
 /* The host's same-template predicate on two queued pods (ksg_compile handles), compiled as a batch with
@@ -458,10 +460,13 @@ int ksg_debug_sched_same(ksg_ctx *ctx, int32_t handle_a, int32_t handle_b);
  * adaptive default, included), a profile without score plugins, OpportunisticBatching acting, or a batch holding a pod
  * with status.nominatedNodeName -- a batch's runs of PodTopologySpread / InterPodAffinity pods go through k_agg_loop's
  * sampling instances: the loop cuts the feasible list to numFeasibleNodesToFind and carries the rotation itself.
- * Unsharded batch calls only, without a PreFilterResult subset and undiagnosed; node-sharded contexts, the resident
- * one-pod calls and ksg_schedule_*_diag keep the per-pod launches for such pods.  false: every sampled
- * PodTopologySpread / InterPodAffinity pod takes the per-pod launches, as before the key existed.  The results are
- * the same either way; ksg_last_batch_kernel_stats names the kernel a batch's pods mostly ran in. */
+ * Unsharded batch calls only, without a PreFilterResult subset; node-sharded contexts, the resident one-pod calls and
+ * ksg_schedule_one_diag keep the per-pod launches for such pods.  false: every sampled PodTopologySpread /
+ * InterPodAffinity pod takes the per-pod launches, as before the key existed.  ksg_schedule_batch_diag runs them in
+ * the diagnosing twins of those instances, which reduce a FitError's statuses inside the loop (config
+ * "aggLoopSampledDiag", default true); false: a diagnosed batch's sampled pods of this class take
+ * the per-pod launches and k_diag_reduce, as before that key existed.  The results and diagnoses are the same either
+ * way; ksg_last_batch_kernel_stats names the kernel a batch's pods mostly ran in. */
 
 /* Parity diagnostic (no device needed): fills out[k] = math.Log(float64(k)) for 0 <= k < n with
  * the table PodTopologySpread's score kernel reads (topologyNormalizingWeight, podtopologyspread/

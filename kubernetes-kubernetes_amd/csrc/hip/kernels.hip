@@ -3560,7 +3560,7 @@ __device__ __forceinline__ void apply_entry(const MirrorView& m, const uint8_t* 
 template <bool SHARD, bool PTSS, bool RING, int MS, bool GRP, bool DIAG = false, bool SAMP = false>
 __device__ __forceinline__ void agg_loop_body(const MirrorView& m, const BatchView& b, const AggView& av, const int w_grp) {
   static_assert(!DIAG || !RING, "the diagnosing instances: batch runs");
-  static_assert(!SAMP || (!SHARD && !RING && !GRP && !DIAG), "the sampling instances: unsharded, undiagnosed batch runs");
+  static_assert(!SAMP || (!SHARD && !RING && !GRP), "the sampling instances: unsharded batch runs");
   constexpr bool kPxa = RING || MS < kMaxSweep;  // phase 1 guesses the PTS raw scores (AG_PXA)
   constexpr int kBlob = RING ? kBlobLds : kAggBlobLds;       // program slot bytes (desc.h)
   constexpr uint32_t kLp = RING ? kAggRingPods : kAggPods;     // LDS list entries (the rest spill to HBM)
@@ -7896,6 +7896,122 @@ hipError_t launch_sched_same(const MirrorView& m, const BatchView& b, const Loop
   if (t0) hipExtLaunchKernelGGL(fn, dim3(1), dim3(kSameThreads), 0, s, t0, t1, 0, m, b, lv);
   else hipLaunchKernelGGL(fn, dim3(1), dim3(kSameThreads), 0, s, m, b, lv);
   return hipGetLastError();
+}
+
+// =====================================================================================================
+// k_same_diag -- the FitError diagnosis of a k_sched_same run, behind it on the stream
+// =====================================================================================================
+// A pod of the run that finds no node assumes nothing, so the run's FitError pods are a suffix [qf, npods) of it,
+// all of them saw one cluster state, and that state is the mirror as the run left it (the kernel boundary makes the
+// commit lanes' column stores visible).  Node blocks of kBlock threads (at most kSameMaxNodes / kBlock of them): the
+// run's last result decides, workgroup-uniformly, whether there is anything to do -- mostly not.  Otherwise every
+// node is evaluated as it is with the scan waves' fill evaluation and diag_accumulate adds the statuses into pod
+// qf's row; the last block to arrive (k_select's ticket: the adds are performed before the ticket is taken, both
+// are agent-scope atomics, and the row is read back with agent-scope loads) copies that row to the rows of the pods
+// behind qf, which are still zero and which nothing else adds to.  No spin, no cross-block wait.  The ticket is
+// PodStats::done of pod qf: zero since the host cleared it, no other kernel runs for that pod.
+__global__ __launch_bounds__(kBlock) void k_same_diag(MirrorView m, BatchView b, int first_pod, int npods, int32_t* rows) {
+  __shared__ __align__(16) uint8_t s_blob[kBlobLds];
+  __shared__ DiagLds s_dg;
+  __shared__ int s_qf;
+  __shared__ uint32_t s_last;
+  auto fit_error = [&](int q) {
+    const DevResult& r = b.results[first_pod + q];
+    return r.feasible == 0 && (r.status == (int32_t)C_UNSCHED || r.status == (int32_t)C_UU);
+  };
+  if (npods < 1 || !fit_error(npods - 1)) return;  // workgroup-uniform
+  const int tid = (int)threadIdx.x, lane = tid & 63;
+  if (tid <= DG_BINS) reinterpret_cast<uint32_t*>(&s_dg)[tid] = 0u;
+  if (tid == 0) s_qf = npods - 1;
+  const uint8_t* g = b.descs + b.desc_off[first_pod];
+  const uint32_t bytes = reinterpret_cast<const PodDesc*>(g)->blob_bytes;
+  stage_blob(g, bytes < (uint32_t)kBlobLds ? bytes : (uint32_t)kBlobLds, s_blob);  // (<= kBlobLds: host-checked)
+  __syncthreads();
+  // qf: the first FitError pod of the run (the pods behind it are FitErrors too)
+  int q0 = npods;
+  for (int q = tid; q < npods; q += kBlock) q0 = fit_error(q) && q < q0 ? q : q0;
+  for (int o = 32; o > 0; o >>= 1) {
+    const int x = __shfl_xor(q0, o, 64);
+    q0 = x < q0 ? x : q0;
+  }
+  if (lane == 0 && q0 < npods) atomicMin(&s_qf, q0);
+  __syncthreads();
+  const int qf = s_qf;
+  const uint8_t* base = s_blob;
+  const PodDesc& d = *reinterpret_cast<const PodDesc*>(base);
+  const PodFast pf = load_fast(base, d);
+  const int i = (int)blockIdx.x * kBlock + tid;
+  const bool valid = i < m.n;
+  uint32_t st = 0;
+  if (valid) st = same_eval(m, load_core<false>(m, i), 0, pf, base, d, i).st;
+  int32_t* row = rows + (size_t)(first_pod + qf) * kDiagWords;
+  diag_accumulate(st, valid, row, s_dg, kBlock / 64);
+  // every wave's adds (the last wave of diag_flush issued them) have been performed before the ticket is taken
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+  if (tid == 0) {
+    const uint32_t t = __hip_atomic_fetch_add(&b.stats[first_pod + qf].done, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    s_last = t == gridDim.x - 1u ? 1u : 0u;
+  }
+  __syncthreads();
+  if (!s_last || qf + 1 >= npods) return;
+  // ---- last block: row qf, complete, to the rows of pods qf+1 .. npods-1 (thread t keeps word t % kDiagWords)
+  static_assert(kBlock % kDiagWords == 0, "k_same_diag: a thread copies one word of every row it visits");
+  const int wd = tid % kDiagWords;
+  const int32_t v = wd < DG_BINS ? __hip_atomic_load(row + wd, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0;
+  const int nw = (npods - 1 - qf) * kDiagWords;
+  for (int k = tid; k < nw; k += kBlock) row[kDiagWords + k] = v;
+}
+hipError_t launch_same_diag(const MirrorView& m, const BatchView& b, int first_pod, int npods, int32_t* rows, hipStream_t s) {
+  if (npods < 1 || npods > kLoopMaxPods || m.n > kSameMaxNodes || rows == nullptr) return hipErrorInvalidValue;
+  if (m.n < 1) return hipSuccess;  // no node, no status: the rows stay zero
+  hipLaunchKernelGGL(k_same_diag, dim3((m.n + kBlock - 1) / kBlock), dim3(kBlock), 0, s, m, b, first_pod, npods, rows);
+  return hipGetLastError();
+}
+
+// The diagnosing twins of k_agg_loop's sampling instances (config "aggLoopSampledDiag"): a diagnosed batch's runs of
+// DF_ROTDEV pods.  Phase 1 stores s_st and the commit's F == 0 branch reduces it as in the unsampled diagnosing
+// instances; F there is exchange A's global, uncut count, and a sampled pod with F == 0 has no cut -- it processed
+// all N nodes -- so the workgroups' words cover every node.  Defined behind every other kernel.
+template <bool PTSS, int MS>
+__global__ __launch_bounds__(kAggThreads) void k_agg_loop_samp_diag(MirrorView m, BatchView b, AggView av) {
+  const AggGroupArg& a = *(const AggGroupArg*)__builtin_amdgcn_kernarg_segment_ptr();  // (k_sched_loop)
+  agg_loop_body<false, PTSS, false, MS, false, true, true>(a.m, a.b, a.av, 0);
+}
+hipError_t launch_agg_loop_samp_diag(const MirrorView& m, const BatchView& b, const AggView& av, hipStream_t s,
+                                     hipEvent_t t0, hipEvent_t t1) {
+  if (av.ring != nullptr || av.world > 1 || av.diag == nullptr) return hipErrorInvalidValue;
+  auto go = [&](auto kern) {
+    if (t0)
+      hipExtLaunchKernelGGL(kern, dim3(av.nwg), dim3(kAggThreads), 0, s, t0, t1, 0, m, b, av);
+    else
+      hipLaunchKernelGGL(kern, dim3(av.nwg), dim3(kAggThreads), 0, s, m, b, av);
+  };
+  if (av.ptss && av.nwg <= 64) go(k_agg_loop_samp_diag<true, 1>);
+  else if (av.ptss) go(k_agg_loop_samp_diag<true, kMaxSweep>);
+  else if (av.nwg <= 64) go(k_agg_loop_samp_diag<false, 1>);
+  else go(k_agg_loop_samp_diag<false, kMaxSweep>);
+  return hipGetLastError();
+}
+// their code (and k_same_diag's) loaded before the first batch, and the workgroups of the largest twin one CU holds
+hipError_t agg_samp_diag_occupancy(int* occ) {
+  const void* fs[] = {reinterpret_cast<const void*>(&k_agg_loop_samp_diag<true, 1>),
+                      reinterpret_cast<const void*>(&k_agg_loop_samp_diag<true, kMaxSweep>),
+                      reinterpret_cast<const void*>(&k_agg_loop_samp_diag<false, 1>),
+                      reinterpret_cast<const void*>(&k_agg_loop_samp_diag<false, kMaxSweep>)};
+  hipFuncAttributes a;
+  hipError_t e = hipFuncGetAttributes(&a, reinterpret_cast<const void*>(&k_same_diag));
+  if (e != hipSuccess) return e;
+  *occ = 1 << 30;
+  for (const void* f : fs) {
+    e = hipFuncGetAttributes(&a, f);
+    if (e != hipSuccess) return e;
+    int o = 0;
+    e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&o, f, kAggThreads, 0);
+    if (e != hipSuccess) return e;
+    *occ = o < *occ ? o : *occ;
+  }
+  return hipSuccess;
 }
 
 }  // namespace ksg

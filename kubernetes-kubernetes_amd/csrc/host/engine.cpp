@@ -113,6 +113,12 @@ hipError_t loop_occupancy(int (&occ)[4]);
 hipError_t launch_agg_loop_samp(const MirrorView& m, const BatchView& b, const AggView& av, hipStream_t s, hipEvent_t t0,
                                 hipEvent_t t1);
 hipError_t agg_samp_occupancy(int* occ);
+// ... and their diagnosing twins (a diagnosed batch, config "aggLoopSampledDiag")
+hipError_t launch_agg_loop_samp_diag(const MirrorView& m, const BatchView& b, const AggView& av, hipStream_t s,
+                                     hipEvent_t t0, hipEvent_t t1);
+hipError_t agg_samp_diag_occupancy(int* occ);
+// k_same_diag: the FitError rows of a k_sched_same run, behind it on the stream (config "loopSameDiag")
+hipError_t launch_same_diag(const MirrorView& m, const BatchView& b, int first_pod, int npods, int32_t* rows, hipStream_t s);
 
 #define HIPCHK(x)                                               \
   do {                                                          \
@@ -1056,7 +1062,8 @@ Engine::Engine(Cluster* cl) : c(cl) {
   if (c->err.empty() && (warm_kernels() != hipSuccess || warm_aggregate() != hipSuccess || warm_kernels_nom() != hipSuccess))
     c->err = "cannot load the kernels' code object on HIP device " + std::to_string(c->cfg.device);
   if (c->err.empty() && (loop_occupancy(loop_occ) != hipSuccess || loop_occupancy_nom(loop_occ_nom) != hipSuccess ||
-                         agg_samp_occupancy(&agg_samp_occ) != hipSuccess))
+                         agg_samp_occupancy(&agg_samp_occ) != hipSuccess ||
+                         agg_samp_diag_occupancy(&agg_samp_diag_occ) != hipSuccess))
     c->err = "cannot query the persistent loops' occupancy on HIP device " + std::to_string(c->cfg.device);
 }
 
@@ -1219,12 +1226,14 @@ bool Engine::agg_loop_ok(const CompiledPod& p, bool resident) const {
     return false;
   // sampled pods (percentageOfNodesToScore / no-score profiles / a nominated pod in the batch): the loop's sampling
   // instances cut the list and carry nextStartNodeIndex themselves, under loop_ok's rule -- batch
-  // runs, unsharded, over the whole snapshot (DF_SUBSET / DF_PREFILTER_REJECT are refused above) -- and undiagnosed
-  // (a diagnosed batch's sampled pods keep the launch path and k_diag_reduce); their residency is the other
-  // instances' (run_batch checks loop_occ[2])
-  if ((d.flags & DF_ROTDEV) &&
-      (!c->cfg.agg_loop_sampled || resident || comm || (d.flags & DF_DIAG) || agg_samp_occ < loop_occ[2]))
-    return false;
+  // runs, unsharded, over the whole snapshot (DF_SUBSET / DF_PREFILTER_REJECT are refused above); a diagnosed
+  // batch's sampled pods take the diagnosing twins ("aggLoopSampledDiag"; false: they keep the launch path and
+  // k_diag_reduce); the instances the batch will run must be as resident as the others (run_batch checks loop_occ[2])
+  if (d.flags & DF_ROTDEV) {
+    if (!c->cfg.agg_loop_sampled || resident || comm) return false;
+    if ((d.flags & DF_DIAG) && !c->cfg.agg_loop_sampled_diag) return false;
+    if (((d.flags & DF_DIAG) ? agg_samp_diag_occ : agg_samp_occ) < loop_occ[2]) return false;
+  }
   // the fold plan holds <= 8 items per kind of the next pod's constraints / terms plus one per own
   // term of the pod just placed (kFoldMax = 80 in k_agg_loop)
   if (d.n_own_terms > 4 * kAggMaxTerms) return false;
@@ -1564,16 +1573,17 @@ static bool agg_same(const CompiledPod& a, const CompiledPod& b) { return !a.err
 // assumed on the device, over the whole snapshot, and whose AssumePod writes nothing a Filter of the next pod reads
 // beyond the core columns (no host port, no scalar resource).  sampled ("loopSameSampled"): also the pods whose
 // nextStartNodeIndex lives on the device (DF_ROTDEV), with or without a cut (DF_SAMPLE) -- the kernel's sampled instance.
-bool Engine::same_eligible(const CompiledPod& p, bool sampled) {
+// diag ("loopSameDiag"): also the pods of a diagnosed batch (DF_DIAG) -- k_same_diag reduces a run's FitErrors behind it.
+bool Engine::same_eligible(const CompiledPod& p, bool sampled, bool diag) {
   if (p.error || p.blob.size() < sizeof(PodDesc) || p.blob.size() > (size_t)kBlobLds || p.blob.size() % 16 != 0) return false;
   PodDesc d;
   std::memcpy(&d, p.blob.data(), sizeof(PodDesc));
   constexpr uint32_t need = DF_FAST | DF_RAW0 | DF_ASSUME;
   constexpr uint32_t rotating = DF_ROTDEV | DF_SAMPLE;
-  constexpr uint32_t never = DF_SUBSET | DF_EARLY | DF_DIAG | DF_NOM_TOPO | DF_PREFILTER_REJECT |
+  constexpr uint32_t never = DF_SUBSET | DF_EARLY | DF_NOM_TOPO | DF_PREFILTER_REJECT |
                              DF_SCORE_ERROR | DF_EVAL_OUT | DF_ALL_FEASIBLE | DF_NODE_LIST | DF_NO_SCORE | DF_AGGREGATE;
-  return (d.flags & need) == need && !(d.flags & never) && (sampled || !(d.flags & rotating)) && d.n_pod_ports == 0 &&
-         d.n_a_scalar == 0 && d.node_name == -1;
+  return (d.flags & need) == need && !(d.flags & never) && (sampled || !(d.flags & rotating)) &&
+         (diag || !(d.flags & DF_DIAG)) && d.n_pod_ports == 0 && d.n_a_scalar == 0 && d.node_name == -1;
 }
 // Pod b may follow pod a in one run: both eligible and one program, byte for byte, but for the fields neither the
 // evaluation nor the selection of the run reads from the shared copy -- the pod-table slot and the rotation start
@@ -2665,16 +2675,17 @@ int Engine::run_batch(const std::vector<const PodSpec*>& pods, const std::vector
     htrace("staged", i);
     return r2;
   };
-  // k_sched_same's launches: unsharded batch runs without a nominee table, a diagnosis, stamps or a forced
-  // give-up, over at most kSameMaxNodes nodes
-  const bool same_ok = use_loop && c->cfg.loop_same_template && W == 1 && !comm && m.nom == nullptr && !diag &&
-                       !c->cfg.loop_stamps && c->cfg.debug_give_up_at < 0 && m.n <= kSameMaxNodes;
+  // k_sched_same's launches: unsharded batch runs without a nominee table, stamps or a forced give-up, over at
+  // most kSameMaxNodes nodes; a diagnosed batch's with "loopSameDiag", k_same_diag behind each
+  const bool same_ok = use_loop && c->cfg.loop_same_template && W == 1 && !comm && m.nom == nullptr &&
+                       (!diag || c->cfg.loop_same_diag) && !c->cfg.loop_stamps && c->cfg.debug_give_up_at < 0 &&
+                       m.n <= kSameMaxNodes;
   int ss_at = -1, ss_len = 0;  // the last stretch measured
   // pods [a, a + result) are eligible and of one template (within the chunk and a launch's pod limit)
   auto same_stretch = [&](int a, int cut) -> int {
     if (a == ss_at) return ss_len;
     int e = a;
-    if (same_eligible(cp[a], c->cfg.loop_same_sampled))
+    if (same_eligible(cp[a], c->cfg.loop_same_sampled, c->cfg.loop_same_diag))
       for (e = a + 1; e < n && e < cut && e - a < kLoopMaxPods && same_programs(cp[e - 1], cp[e]);) ++e;
     ss_at = a;
     return ss_len = e - a;
@@ -2749,6 +2760,8 @@ int Engine::run_batch(const std::vector<const PodSpec*>& pods, const std::vector
         // (rotdev() is per batch: the run's pods all carry DF_ROTDEV, or none does)
         HIPCHK(launch_sched_same(m, bv, lv, s, t0, t1,
                                  (reinterpret_cast<const PodDesc*>(cp[i].blob.data())->flags & DF_ROTDEV) != 0));
+        // the run's FitErrors: a suffix of it, reduced once from the mirror as the run leaves it
+        if (diag) HIPCHK(launch_same_diag(m, bv, i, j - i, (int32_t*)d_diag.p, s));
       } else {
         HIPCHK(launch_sched_loop(m, bv, lv, s, t0, t1, unit));
       }
@@ -2842,6 +2855,8 @@ int Engine::run_batch(const std::vector<const PodSpec*>& pods, const std::vector
         req.t0 = t0;
         req.t1 = t1;
         if ((rc = group_launch(&req, true, G, 0))) return rc;
+      } else if (samp && av.diag != nullptr) {
+        HIPCHK(launch_agg_loop_samp_diag(m, bv, av, s, t0, t1));
       } else if (samp) {
         HIPCHK(launch_agg_loop_samp(m, bv, av, s, t0, t1));
       } else {

@@ -253,6 +253,11 @@ struct Config {
   // k_agg_loop: batch runs of sampled pods (DF_ROTDEV: percentageOfNodesToScore < 100, a no-score profile, a
   // nominated pod in the batch) through its sampling instances ("aggLoopSampled"; false: the launch path, as before)
   bool agg_loop_sampled = true;
+  // a diagnosed batch (ksg_schedule_batch_diag) on the two paths above: k_sched_same's runs with
+  // k_same_diag behind each ("loopSameDiag"), and sampled pods in k_agg_loop's diagnosing sampling instances
+  // ("aggLoopSampledDiag"); false: such a batch is routed as before (k_sched_loop / the launch path)
+  bool loop_same_diag = true;
+  bool agg_loop_sampled_diag = true;
   bool resident_ahead = true;  // resident loops: the next pod's phase 1 ahead of its doorbell (LoopView, AggView bit 7)
   int debug_give_up_at = -1;    // diagnostic: the persistent loops give up at this pod of a run
   int loop_wg = 0;              // k_sched_loop workgroups (0: min(node units, CUs, 128))
@@ -641,8 +646,9 @@ class Engine {
   // pods of k_sched_loop's runs that k_sched_same ran, and that k_sched_loop ran (ksg_debug_same_pods)
   uint64_t same_pods_ = 0, not_same_pods_ = 0;
   // a pod k_sched_same can take, and whether pod b may follow pod a in one of its runs (engine.cpp)
-  // (sampled: config loop_same_sampled -- pods with a device-resident nextStartNodeIndex too)
-  static bool same_eligible(const CompiledPod& p, bool sampled);
+  // (sampled: config loop_same_sampled -- pods with a device-resident nextStartNodeIndex too; diag: config
+  // loop_same_diag -- pods of a diagnosed batch too)
+  static bool same_eligible(const CompiledPod& p, bool sampled, bool diag = true);
   static bool sched_same(const CompiledPod& a, const CompiledPod& b, bool sampled);
   int run_plugin(const PodSpec& p, Mode mode, int plugin, const uint8_t* nodes, int32_t* code, uint8_t* codes,
                  uint32_t* reasons, int64_t* raw, int64_t* norm);
@@ -669,6 +675,7 @@ class Engine {
   // group launches when a nominee table is staged
   int loop_occ_nom[2] = {0, 0};
   int agg_samp_occ = 0;  // ... of k_agg_loop's sampling instances (agg_samp_occupancy), which a run of sampled pods takes
+  int agg_samp_diag_occ = 0;  // ... of their diagnosing twins (agg_samp_diag_occupancy): such a run of a diagnosed batch
   bool loop_ok(const CompiledPod& p) const;
   bool loop_bounds_ok(const CompiledPod& p) const;  // the loops' granule payload bounds
   // resident: a resident one-pod call (the ring's instance carries no sampling)
