@@ -460,13 +460,23 @@ int ksg_debug_sched_same(ksg_ctx *ctx, int32_t handle_a, int32_t handle_b);
  * adaptive default, included), a profile without score plugins, OpportunisticBatching acting, or a batch holding a pod
  * with status.nominatedNodeName -- a batch's runs of PodTopologySpread / InterPodAffinity pods go through k_agg_loop's
  * sampling instances: the loop cuts the feasible list to numFeasibleNodesToFind and carries the rotation itself.
- * Unsharded batch calls only, without a PreFilterResult subset; node-sharded contexts, the resident one-pod calls and
- * ksg_schedule_one_diag keep the per-pod launches for such pods.  false: every sampled PodTopologySpread /
+ * Unsharded calls only, without a PreFilterResult subset; node-sharded contexts and ksg_schedule_one_diag keep the
+ * per-pod launches for such pods.  ksg_schedule_one of such a pod (KSG_FLAG_ASSUME, no evaluation output) is served by
+ * the resident k_agg_loop's sampling instances (config "residentAggSampled", default true; needs "aggLoopSampled";
+ * DESIGN.md §4.5 "Resident k_agg_loop"): the host stays the authority on nextStartNodeIndex, which travels with every
+ * pod's doorbell and comes back with its result; false: those calls keep the per-pod launches, as before that key
+ * existed.  "aggLoopSampled" false: every sampled PodTopologySpread /
  * InterPodAffinity pod takes the per-pod launches, as before the key existed.  ksg_schedule_batch_diag runs them in
  * the diagnosing twins of those instances, which reduce a FitError's statuses inside the loop (config
  * "aggLoopSampledDiag", default true); false: a diagnosed batch's sampled pods of this class take
  * the per-pod launches and k_diag_reduce, as before that key existed.  The results and diagnoses are the same either
  * way; ksg_last_batch_kernel_stats names the kernel a batch's pods mostly ran in. */
+
+/* Where the one-pod calls went: of the ksg_schedule_one calls since the context was created that may take a resident
+ * loop at all (KSG_FLAG_ASSUME, no evaluation output, no diagnosis, not a pod the nominator holds), those the resident
+ * k_sched_loop served (*sched), those the resident k_agg_loop served (*agg) and those that took the per-pod launches
+ * (*launch).  Counted on the host; a call decided on the host (a PreFilter rejection) or failed is in none of them. */
+int ksg_debug_resident_calls(const ksg_ctx *ctx, uint64_t *sched, uint64_t *agg, uint64_t *launch);
 
 /* Parity diagnostic (no device needed): fills out[k] = math.Log(float64(k)) for 0 <= k < n with
  * the table PodTopologySpread's score kernel reads (topologyNormalizingWeight, podtopologyspread/

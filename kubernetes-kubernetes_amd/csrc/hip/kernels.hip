@@ -3556,12 +3556,18 @@ __device__ __forceinline__ void apply_entry(const MirrorView& m, const uint8_t* 
 // exchange (M, the granule row at q + kLoopMaxPods, exchange A's slot meanings) carries the kept nodes' maxima /
 // minima, PodTopologySpread presence bits and non-ignored count, and the (K+1)-th node's processedNodes + 1 from the
 // workgroup that holds it; phase 2 keeps the rotated positions < K.  The other instances compile none of it.
+// SAMP with RING (k_agg_loop_ring_samp, ksg_schedule_one of sampled pods): the host stays the authority on
+// nextStartNodeIndex -- thread 0 sets s_rot[q & 1] from pod q's program once it is in LDS (staged, or copied and
+// patched from the doorbell), before phase 1 or the count ahead of the doorbell reads it; the loop's own advance into
+// s_rot[(q + 1) & 1] goes back to the host with the result (rot_stats) and is overwritten by the next pod's.
 // (the body of k_agg_loop and k_agg_loop_group: w = the workgroup this block plays in its rank)
 template <bool SHARD, bool PTSS, bool RING, int MS, bool GRP, bool DIAG = false, bool SAMP = false>
 __device__ __forceinline__ void agg_loop_body(const MirrorView& m, const BatchView& b, const AggView& av, const int w_grp) {
   static_assert(!DIAG || !RING, "the diagnosing instances: batch runs");
-  static_assert(!SAMP || (!SHARD && !RING && !GRP), "the sampling instances: unsharded batch runs");
-  constexpr bool kPxa = RING || MS < kMaxSweep;  // phase 1 guesses the PTS raw scores (AG_PXA)
+  static_assert(!SAMP || (!SHARD && !GRP), "the sampling instances: unsharded runs");
+  static_assert(!SAMP || !RING || PTSS, "the resident sampling instances: with PodTopologySpread scoring");
+  // phase 1 guesses the PTS raw scores (AG_PXA); the resident sampling instance for large grids goes without (registers)
+  constexpr bool kPxa = (RING && !SAMP) || MS < kMaxSweep;
   constexpr int kBlob = RING ? kBlobLds : kAggBlobLds;       // program slot bytes (desc.h)
   constexpr uint32_t kLp = RING ? kAggRingPods : kAggPods;     // LDS list entries (the rest spill to HBM)
   constexpr uint32_t kLt = RING ? kAggRingTerms : kAggTerms;
@@ -4356,9 +4362,14 @@ __device__ __forceinline__ void agg_loop_body(const MirrorView& m, const BatchVi
   if constexpr (SAMP) {
     // the run's first pod: the previous launched pod's nextStartNodeIndex, or the host's (read before phase 1
     // of pod 0, behind the barriers of its gather)
+    // (resident: no program is staged yet; every pod's start comes with its program, below)
     if (t == 0 && av.npods > 0) {
-      const PodDesc& d0 = *reinterpret_cast<const PodDesc*>(s_blob[0]);
-      s_rot[0] = d0.prev_pod < 0 ? b.stats[av.first_pod].rot_in : b.stats[d0.prev_pod].rot_out;
+      if constexpr (RING) {
+        s_rot[0] = 0u;
+      } else {
+        const PodDesc& d0 = *reinterpret_cast<const PodDesc*>(s_blob[0]);
+        s_rot[0] = d0.prev_pod < 0 ? b.stats[av.first_pod].rot_in : b.stats[d0.prev_pod].rot_out;
+      }
       s_rot[1] = 0u;
       s_samp[0] = 0u;
       s_samp[1] = ~0u;
@@ -4522,6 +4533,12 @@ __device__ __forceinline__ void agg_loop_body(const MirrorView& m, const BatchVi
       // the same template as pod q-1 (host: DF_AGG_SAME): pod q's counts are q-1's plus q-1's placement,
       // folded into the counts in LDS at the end of pod q-1 already (s_spec_q)
       const PodDesc& dq = *reinterpret_cast<const PodDesc*>(s_blob[q % 3]);
+      if constexpr (SAMP) {
+        // pod q's nextStartNodeIndex is the host's (the previous call's result), whether its program was staged or
+        // copied and patched: set before phase 1 -- or the count ahead of the doorbell -- reads rot_of
+        if (t == 0) s_rot[q & 1] = (uint32_t)dq.rot_start;
+        __syncthreads();
+      }
       ahead = (rmode & RING_SAME) && (dq.flags & DF_AGG_SAME) && s_spec_q == q - 1 && s_ahead_q == q - 1 && q > 0;
       if (!((dq.flags & DF_AGG_SAME) && s_spec_q == q - 1 && q > 0)) {
         aggregate(q, t, kAggThreads, wg_bar);
@@ -8005,6 +8022,41 @@ hipError_t agg_samp_diag_occupancy(int* occ) {
   *occ = 1 << 30;
   for (const void* f : fs) {
     e = hipFuncGetAttributes(&a, f);
+    if (e != hipSuccess) return e;
+    int o = 0;
+    e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&o, f, kAggThreads, 0);
+    if (e != hipSuccess) return e;
+    *occ = o < *occ ? o : *occ;
+  }
+  return hipSuccess;
+}
+
+// The resident sampling instances (agg_loop_body's RING with SAMP; config "residentAggSampled"): ksg_schedule_one of
+// sampled PodTopologySpread / InterPodAffinity pods through the ring.  Two of them, by the grid: the one-round
+// instance (at most 64 workgroups) keeps the PodTopologySpread raw-score guess (AG_PXA) for uncut pods; the four-round
+// one holds four times the exchange registers and goes without it.  Defined behind every other kernel.
+template <int MS>
+__global__ __launch_bounds__(kAggThreads) void k_agg_loop_ring_samp(MirrorView m, BatchView b, AggView av) {
+  const AggGroupArg& a = *(const AggGroupArg*)__builtin_amdgcn_kernarg_segment_ptr();  // (k_sched_loop)
+  agg_loop_body<false, true, true, MS, false, false, true>(a.m, a.b, a.av, 0);
+}
+// (samp_rows: agg_setup allocated the second bank of granule rows, exchange M's)
+hipError_t launch_agg_loop_ring_samp(const MirrorView& m, const BatchView& b, const AggView& av, bool samp_rows,
+                                     hipStream_t s) {
+  if (av.ring == nullptr || av.world > 1 || av.diag != nullptr || !samp_rows || av.npods > kLoopMaxPods)
+    return hipErrorInvalidValue;
+  if (av.nwg <= 64) hipLaunchKernelGGL(k_agg_loop_ring_samp<1>, dim3(av.nwg), dim3(kAggThreads), 0, s, m, b, av);
+  else hipLaunchKernelGGL(k_agg_loop_ring_samp<kMaxSweep>, dim3(av.nwg), dim3(kAggThreads), 0, s, m, b, av);
+  return hipGetLastError();
+}
+// their code loaded before the first call (warm_kernels), and the workgroups of the larger of them one CU holds
+hipError_t agg_ring_samp_occupancy(int* occ) {
+  const void* fs[] = {reinterpret_cast<const void*>(&k_agg_loop_ring_samp<1>),
+                      reinterpret_cast<const void*>(&k_agg_loop_ring_samp<kMaxSweep>)};
+  *occ = 1 << 30;
+  for (const void* f : fs) {
+    hipFuncAttributes a;
+    hipError_t e = hipFuncGetAttributes(&a, f);
     if (e != hipSuccess) return e;
     int o = 0;
     e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&o, f, kAggThreads, 0);

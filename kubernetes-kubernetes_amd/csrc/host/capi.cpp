@@ -342,6 +342,7 @@ static int schedule_one(ksg_ctx* ctx, int32_t handle, uint32_t flags, ksg_result
       bool handled = false;
       const int rc = ctx->engine->schedule_resident(it->second, handle, result, &handled);
       if (handled) return with_err(ctx, rc);
+      ctx->engine->res_calls_[2]++;  // through the gate, to the launch path (ksg_debug_resident_calls)
     }
     if (const int rs = quiesce(ctx)) return rs;
     std::vector<const PodSpec*> pods{&it->second};
@@ -594,6 +595,14 @@ int ksg_debug_loop_stats(const ksg_ctx* ctx, uint64_t* give_ups, uint64_t* retri
   if (!ctx || !give_ups || !retries) return KSG_EINVAL;
   *give_ups = ctx->engine->loop_give_ups_;
   *retries = ctx->engine->loop_retries_;
+  return KSG_OK;
+}
+
+int ksg_debug_resident_calls(const ksg_ctx* ctx, uint64_t* sched, uint64_t* agg, uint64_t* launch) {
+  if (!ctx || !sched || !agg || !launch) return KSG_EINVAL;
+  *sched = ctx->engine->res_calls_[0];
+  *agg = ctx->engine->res_calls_[1];
+  *launch = ctx->engine->res_calls_[2];
   return KSG_OK;
 }
 

@@ -117,6 +117,10 @@ hipError_t agg_samp_occupancy(int* occ);
 hipError_t launch_agg_loop_samp_diag(const MirrorView& m, const BatchView& b, const AggView& av, hipStream_t s,
                                      hipEvent_t t0, hipEvent_t t1);
 hipError_t agg_samp_diag_occupancy(int* occ);
+// ... and the resident sampling instances (ksg_schedule_one of sampled pods, config "residentAggSampled")
+hipError_t launch_agg_loop_ring_samp(const MirrorView& m, const BatchView& b, const AggView& av, bool samp_rows,
+                                     hipStream_t s);
+hipError_t agg_ring_samp_occupancy(int* occ);
 // k_same_diag: the FitError rows of a k_sched_same run, behind it on the stream (config "loopSameDiag")
 hipError_t launch_same_diag(const MirrorView& m, const BatchView& b, int first_pod, int npods, int32_t* rows, hipStream_t s);
 
@@ -1063,7 +1067,8 @@ Engine::Engine(Cluster* cl) : c(cl) {
     c->err = "cannot load the kernels' code object on HIP device " + std::to_string(c->cfg.device);
   if (c->err.empty() && (loop_occupancy(loop_occ) != hipSuccess || loop_occupancy_nom(loop_occ_nom) != hipSuccess ||
                          agg_samp_occupancy(&agg_samp_occ) != hipSuccess ||
-                         agg_samp_diag_occupancy(&agg_samp_diag_occ) != hipSuccess))
+                         agg_samp_diag_occupancy(&agg_samp_diag_occ) != hipSuccess ||
+                         agg_ring_samp_occupancy(&agg_ring_samp_occ) != hipSuccess))
     c->err = "cannot query the persistent loops' occupancy on HIP device " + std::to_string(c->cfg.device);
 }
 
@@ -1228,11 +1233,17 @@ bool Engine::agg_loop_ok(const CompiledPod& p, bool resident) const {
   // instances cut the list and carry nextStartNodeIndex themselves, under loop_ok's rule -- batch
   // runs, unsharded, over the whole snapshot (DF_SUBSET / DF_PREFILTER_REJECT are refused above); a diagnosed
   // batch's sampled pods take the diagnosing twins ("aggLoopSampledDiag"; false: they keep the launch path and
-  // k_diag_reduce); the instances the batch will run must be as resident as the others (run_batch checks loop_occ[2])
+  // k_diag_reduce); the instances the batch will run must be as resident as the others (run_batch checks loop_occ[2]).
+  // A resident one-pod call takes the ring's sampling instances ("residentAggSampled"; false: the launch path; never
+  // diagnosed: ksg_schedule_one_diag does not reach the resident loops)
   if (d.flags & DF_ROTDEV) {
-    if (!c->cfg.agg_loop_sampled || resident || comm) return false;
-    if ((d.flags & DF_DIAG) && !c->cfg.agg_loop_sampled_diag) return false;
-    if (((d.flags & DF_DIAG) ? agg_samp_diag_occ : agg_samp_occ) < loop_occ[2]) return false;
+    if (!c->cfg.agg_loop_sampled || comm) return false;
+    if (resident) {
+      if (!c->cfg.resident_agg_sampled || (d.flags & DF_DIAG) || agg_ring_samp_occ < loop_occ[2]) return false;
+    } else {
+      if ((d.flags & DF_DIAG) && !c->cfg.agg_loop_sampled_diag) return false;
+      if (((d.flags & DF_DIAG) ? agg_samp_diag_occ : agg_samp_occ) < loop_occ[2]) return false;
+    }
   }
   // the fold plan holds <= 8 items per kind of the next pod's constraints / terms plus one per own
   // term of the pod just placed (kFoldMax = 80 in k_agg_loop)
@@ -3705,6 +3716,7 @@ relaunch:
   if (res_running_ && (c->mirror_pending() || nom_stale() || res_q_ >= kLoopMaxPods || res_kind_ != kind ||
                        (kind == 1 && (GS != res_gs_ || unit != res_unit_)) || (kind == 2 && G != res_gs_) ||
                        (kind == 2 && res_terms_ + cp.own_terms > kRingTermBudget) ||
+                       (kind == 2 && res_samp_ != rot_dev) ||  // (the other family of k_agg_loop's resident instances)
                        clk::now() - res_last_ > std::chrono::milliseconds(kResidentIdleMs / 2)))
     if ((rc = resident_stop())) return fail(rc);
   if (!res_running_) {
@@ -3829,7 +3841,15 @@ relaunch:
         HIPCHK(hipMemsetAsync(d_astamps.p, 0, sb, s));
         av.stamps = (unsigned long long*)d_astamps.p;
       }
-      HIPCHK(launch_agg_loop(c->view, bview(kLoopMaxPods), av, s, nullptr, nullptr));
+      // sampled pods (rotdev(): every pod of the launch carries DF_ROTDEV): the sampling instances, whose exchange M
+      // uses the second bank of granule rows agg_setup allocates with "aggLoopSampled" on
+      if (rot_dev) {
+        const bool samp_rows = d_agran.bytes >= (size_t)2 * kLoopMaxPods * 256 * kAGran * 8;
+        HIPCHK(launch_agg_loop_ring_samp(c->view, bview(kLoopMaxPods), av, samp_rows, s));
+      } else {
+        HIPCHK(launch_agg_loop(c->view, bview(kLoopMaxPods), av, s, nullptr, nullptr));
+      }
+      res_samp_ = rot_dev;
       res_gs_ = G;
       res_terms_ = 0;
     }
@@ -4009,6 +4029,7 @@ relaunch:
     c->pod_table_drop(cp.slot);
   }
   last_kernel = kind == 2 ? 2 : 1;
+  res_calls_[kind == 2 ? 1 : 0]++;
   if (c->cfg.loop_stamps) {
     auto us = [](clk::time_point a, clk::time_point b) { return std::chrono::duration<double, std::micro>(b - a).count(); };
     res_prof_[0] += us(T0, T1);

@@ -253,6 +253,9 @@ struct Config {
   // k_agg_loop: batch runs of sampled pods (DF_ROTDEV: percentageOfNodesToScore < 100, a no-score profile, a
   // nominated pod in the batch) through its sampling instances ("aggLoopSampled"; false: the launch path, as before)
   bool agg_loop_sampled = true;
+  // ... and ksg_schedule_one of such pods through the resident k_agg_loop's sampling instances
+  // ("residentAggSampled"; needs aggLoopSampled; false: those calls keep the per-pod launches, as before)
+  bool resident_agg_sampled = true;
   // a diagnosed batch (ksg_schedule_batch_diag) on the two paths above: k_sched_same's runs with
   // k_same_diag behind each ("loopSameDiag"), and sampled pods in k_agg_loop's diagnosing sampling instances
   // ("aggLoopSampledDiag"); false: such a batch is routed as before (k_sched_loop / the launch path)
@@ -676,9 +679,13 @@ class Engine {
   int loop_occ_nom[2] = {0, 0};
   int agg_samp_occ = 0;  // ... of k_agg_loop's sampling instances (agg_samp_occupancy), which a run of sampled pods takes
   int agg_samp_diag_occ = 0;  // ... of their diagnosing twins (agg_samp_diag_occupancy): such a run of a diagnosed batch
+  int agg_ring_samp_occ = 0;  // ... of the resident sampling instances (agg_ring_samp_occupancy): sampled one-pod calls
+  // ksg_schedule_one calls through schedule_resident's gate (assume, no evaluation, no diagnosis) since creation:
+  // served by the resident k_sched_loop, by the resident k_agg_loop, by the launch path (ksg_debug_resident_calls)
+  uint64_t res_calls_[3] = {0, 0, 0};
   bool loop_ok(const CompiledPod& p) const;
   bool loop_bounds_ok(const CompiledPod& p) const;  // the loops' granule payload bounds
-  // resident: a resident one-pod call (the ring's instance carries no sampling)
+  // resident: a resident one-pod call (sampled pods: the ring's sampling instances, cfg.resident_agg_sampled)
   bool agg_loop_ok(const CompiledPod& p, bool resident = false) const;
   // node-sharded evaluation (cfg.world > 1): this rank's block range + the exchange transport
   std::unique_ptr<Comm> comm;
@@ -785,6 +792,7 @@ class Engine {
   std::vector<uint8_t> res_prev_blob_, res_prev_entry_;  // k_agg_loop ring: the program / entry posted last
   long res_posts_[12] = {};  // k_agg_loop ring posts: same, RING_TERMS, staged (+ ring_terms_patch's why) (loopStamps)
   int res_kind_ = 0;              // the running launch: 1 k_sched_loop, 2 k_agg_loop (pod-table pods)
+  bool res_samp_ = false;         // ... launched under rotdev(): k_agg_loop's sampling instances (sampled pods)
   int64_t res_terms_ = 0;         // k_agg_loop: own affinity terms of the pods posted (its spill rows' budget)
   std::chrono::steady_clock::time_point res_last_{};  // the last result the host took
   double res_prof_[5] = {};       // loopStamps: compile / post / device / settle us, calls

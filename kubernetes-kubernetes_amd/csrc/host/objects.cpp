@@ -927,6 +927,7 @@ bool decode_config(const char* p, size_t n, Config* c, std::string* err) {
     c->loop_same_min_run = std::max(1, (int)d.num(r, "loopSameMinRun", c->loop_same_min_run));
     if (const JVal* ss = d.get(r, "loopSameSampled")) c->loop_same_sampled = !(ss->type == JVal::BOOL && !ss->b);
     if (const JVal* as = d.get(r, "aggLoopSampled")) c->agg_loop_sampled = !(as->type == JVal::BOOL && !as->b);
+    if (const JVal* rs = d.get(r, "residentAggSampled")) c->resident_agg_sampled = !(rs->type == JVal::BOOL && !rs->b);
     if (const JVal* sd = d.get(r, "loopSameDiag")) c->loop_same_diag = !(sd->type == JVal::BOOL && !sd->b);
     if (const JVal* ad = d.get(r, "aggLoopSampledDiag")) c->agg_loop_sampled_diag = !(ad->type == JVal::BOOL && !ad->b);
     if (const JVal* ra = d.get(r, "residentAhead")) c->resident_ahead = !(ra->type == JVal::BOOL && !ra->b);

@@ -150,6 +150,17 @@ class Scheduler(Backend):
         self._chk(fn(self.ctx, C.byref(a), C.byref(b)), "same_pods")
         return a.value, b.value
 
+    def resident_calls(self):
+        """(sched, agg, launch): the schedule_one(assume=True) calls without evaluation or diagnosis so far that the
+        resident k_sched_loop served, that the resident k_agg_loop served, and that took the launch path
+        (ksg_debug_resident_calls; bound on first use, as lean_pods)."""
+        fn = self.lib.ksg_debug_resident_calls
+        fn.restype = C.c_int
+        fn.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+        a, b, l = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        self._chk(fn(self.ctx, C.byref(a), C.byref(b), C.byref(l)), "resident_calls")
+        return a.value, b.value, l.value
+
     def sched_same(self, handle_a, handle_b):
         """Whether pod b may follow pod a in a k_sched_same run (ksg_debug_sched_same; schedules nothing)."""
         fn = self.lib.ksg_debug_sched_same

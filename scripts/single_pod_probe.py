@@ -5,7 +5,12 @@ ksg_schedule_batch of the same pods.  Prints one JSON line per workload.
 
   python scripts/single_pod_probe.py [workload ...]     c2 (SchedulingBasic 5000 nodes, default), c2pct0,
                                                         dts (DefaultTopologySpreading), c4 (TopologySpreading
-                                                        15000 nodes), c3, c3aff (C3's pod-affinity pods alone), c4-anti, c5 (100 000 nodes), c2big (SchedulingBasic at 100 000 nodes)
+                                                        15000 nodes), c3, c3aff (C3's pod-affinity pods alone), c4-anti, c5 (100 000 nodes), c2big (SchedulingBasic at 100 000 nodes);
+                                                        dtspct0, c4pct0, c3pct0: the same clusters with
+                                                        percentageOfNodesToScore 0 (the adaptive default) on the
+                                                        device and in the oracle, as c2pct0
+  python scripts/single_pod_probe.py native [workload ...]  the native calls alone, oracle-checked: one line per
+                                                        workload (KSG_LIB names the library: A/B runs of two builds)
   python scripts/single_pod_probe.py stamps [workload]  the resident call's host / device split
   python scripts/single_pod_probe.py ab [workload]      resident variants (residentAhead, the doorbell relay, and
                                                         k_agg_loop's same-template shortcuts off: aggLoopDebug 8 / 12)
@@ -26,8 +31,14 @@ from ksg import synth  # noqa: E402
 from ksg.native import Scheduler  # noqa: E402
 
 
+def pct0(wl):  # percentageOfNodesToScore 0 on the device and in the oracle
+    return wl.endswith("pct0")
+
+
 def cluster(wl, n_pods):
     objects = []
+    if pct0(wl) and wl != "c2pct0":
+        wl = wl[:-len("pct0")]
     if wl in ("c2", "c2pct0"):
         nodes, init, pods = synth.scheduling_basic(5000, 1000, n_pods)
     elif wl == "c2big":  # SchedulingBasic pods on 100 000 nodes
@@ -46,9 +57,32 @@ def cluster(wl, n_pods):
     return nodes, init, pods, objects
 
 
+def oracle_results(wl, nodes, init, pods, objects):
+    """The oracle's result tuple per pod; KSG_PROBE_CACHE names a directory that keeps them per workload between
+    runs (A/B runs of two builds check against one oracle pass)."""
+    cache = os.environ.get("KSG_PROBE_CACHE")
+    path = os.path.join(cache, f"{wl}-{len(pods)}.json") if cache else None
+    if path and os.path.exists(path):
+        with open(path) as f:
+            return [tuple(t) for t in json.load(f)]
+    from oracle_binding import oracle
+    o = oracle(dict(percentageOfNodesToScore=0) if pct0(wl) else {"cpuThreads": 16} if wl in ("c5", "c2big") else {})
+    for ob in objects:
+        o.upsert_object(ob)
+    for n in nodes:
+        o.add_node(n)
+    for p in init:
+        o.add_pod(p)
+    want = [o.schedule_one(o.compile(p), assume=True)[0].as_tuple() for p in pods]
+    if path:
+        with open(path, "w") as f:
+            json.dump(want, f)
+    return want
+
+
 def run(wl, cfg, n_pods=2000, batch=False, check=False, native=False):
     nodes, init, pods, objects = cluster(wl, n_pods + 200)
-    if wl == "c2pct0":
+    if pct0(wl):
         cfg = dict(cfg, percentageOfNodesToScore=0)
     s = Scheduler(cfg)
     for ob in objects:
@@ -73,18 +107,8 @@ def run(wl, cfg, n_pods=2000, batch=False, check=False, native=False):
     s.close()
     mism = None
     if check:
-        from oracle_binding import oracle
-        o = oracle(dict(percentageOfNodesToScore=0) if wl == "c2pct0" else {"cpuThreads": 16} if wl in ("c5", "c2big") else {})
-        for ob in objects:
-            o.upsert_object(ob)
-        for n in nodes:
-            o.add_node(n)
-        for p in init:
-            o.add_pod(p)
-        mism = 0
-        for k, p in enumerate(pods):
-            if o.schedule_one(o.compile(p), assume=True)[0].as_tuple() != got[k]:
-                mism += 1
+        want = oracle_results(wl, nodes, init, pods, objects)
+        mism = sum(w != g for w, g in zip(want, got))
     return dt / n_pods * 1e6, kern, mism
 
 
@@ -101,6 +125,13 @@ def main():
                 nus, _, nmism = run(wl, cfg, check=rep == 0, native=True)
                 print(json.dumps({"workload": wl, "variant": name, "rep": rep, "single_resident_native_us": round(nus, 2),
                                   "native_oracle_mismatches": nmism}), flush=True)
+        return
+    if args[:1] == ["native"]:
+        for wl in args[1:] or ["c2"]:
+            nus, kern, nmism = run(wl, {}, check=True, native=True)
+            print(json.dumps({"workload": wl, "lib": os.environ.get("KSG_LIB", "this tree"),
+                              "single_resident_native_us": round(nus, 2), "resident_kernel": kern,
+                              "native_oracle_mismatches": nmism}), flush=True)
         return
     if args[:1] == ["stamps"]:  # printed at the loop's stop
         wl = args[1] if len(args) > 1 else "c2"
