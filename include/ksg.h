@@ -450,6 +450,26 @@ int ksg_debug_lean_pods(const ksg_ctx *ctx, uint64_t *lean, uint64_t *general);
  * diagnosed batch is taken, as before the key existed; results and diagnoses are the same either way. */
 int ksg_debug_same_pods(const ksg_ctx *ctx, uint64_t *taken, uint64_t *not_taken);
 
+/* The compile memo (config "compileMemo": "on", the default, "off" or "verify").  A scheduling cycle's
+ * host compile keeps the last program it built that depends on nothing of the pod beyond its template -- node-local
+ * plugins only, no node subset, no nomination, no OpportunisticBatching signature -- and the next pod stamped from the
+ * same template (every field of the pod but its name and uid equal, decided at ksg_pod_compile) copies it, with its
+ * own pod-table slot and rotation start, as long as nothing the compile reads of the cluster has changed.
+ * "verify": every such copy is also compiled in full and compared byte for byte; a difference fails the call with
+ * KSG_EINVAL, the error naming the pod and the first differing offset.  *hits: the cycles' compiles served by a
+ * copy since the context was created; *misses: those compiled in full.  Both stay 0 with "off". */
+int ksg_debug_compile_memo(const ksg_ctx *ctx, uint64_t *hits, uint64_t *misses);
+
+/* k_sched_same's carry (config "loopSameCarry", default false).  A k_sched_same launch ends by
+ * writing the state it holds -- every node's total as it is, its score and feasibility with one more template pod on
+ * it -- to a buffer of the engine's, its tag last.  The next launch of the same batch loads that state instead of
+ * evaluating every node twice, when the host can tell that it is what the evaluation would give: the launch before
+ * it on the stream was a k_sched_same run of the same program on the same instance, and nothing touched the mirror in
+ * between.  The kernel loads only if the stored tag is the expected one, so a predecessor that gave up costs time,
+ * never correctness.  *loaded: the launches told to load since the context was created; *filled: the others.  Both
+ * stay 0 with the key off.  Nothing is carried from one batch to the next. */
+int ksg_debug_same_carry(const ksg_ctx *ctx, uint64_t *loaded, uint64_t *filled);
+
 /* The host's same-template predicate on two queued pods (ksg_compile handles), compiled as a batch with
  * KSG_FLAG_ASSUME compiles them: 1 when pod b may follow pod a in a k_sched_same run (both eligible, one program
  * but for slot, rotation start and batch bookkeeping), 0 when not, negative on error.  Schedules nothing. */

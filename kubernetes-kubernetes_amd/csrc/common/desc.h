@@ -709,6 +709,11 @@ struct LoopView {
   // a diagnosed batch run (ksg_schedule_batch_diag): the batch's diagnosis rows, [batch pods][kDiagWords] -- the
   // DIAG instances add a pod's per-node statuses to its row where its cycle ends without a feasible node
   int32_t* diag;
+  // k_sched_same: the engine's carry buffer (kSameCarryWords words; nullptr: config loopSameCarry off).  A launch that
+  // did not give up ends by writing its cached state there, carry_tag last; one whose carry_expect (0: none) equals
+  // the stored tag loads that state instead of evaluating its fill
+  unsigned long long* carry;
+  uint32_t carry_tag, carry_expect;
 };
 // exchange granules per participant per pod: A0 {count, count before nextStartNodeIndex},
 // A1 {max raw TT + 1, max raw NA + 1}, B {packed key < 2^48}, B_node (sharded only) -- four words used, the row
@@ -745,6 +750,10 @@ constexpr int kSameSampledLdsBytes = kSameLdsBytes + kLoopMaxPods * (4 + 4) + 64
 static_assert(kSameLdsBytes <= 160 * 1024 && kSameSampledLdsBytes <= 160 * 1024,
               "k_sched_same: one workgroup's LDS (160 KiB per CU on gfx950)");
 static_assert(kSameGroups <= 128, "k_sched_same: the group prefix scan holds two groups per lane");
+// LoopView::carry: per node its total as it is (0: infeasible) and its post fixed score, the two ballots, the tag
+constexpr int kSameCarryTot = 0, kSameCarryFx1 = kSameMaxNodes, kSameCarryBall0 = 2 * kSameMaxNodes,
+              kSameCarryBall1 = kSameCarryBall0 + kSameGroups, kSameCarryTagWord = kSameCarryBall1 + kSameGroups;
+constexpr int kSameCarryWords = kSameCarryTagWord + 1;
 static_assert(kSameMaxNodes >= 5000, "k_sched_same: the flagship workload's nodes fit");
 
 // ---- persistent loop for pods with pod-table aggregation (k_agg_loop) ---------------

@@ -252,6 +252,7 @@ int ksg_pod_compile(ksg_ctx* ctx, const char* pod_json, size_t len, int32_t* han
     }
     // the pod's pod-table entry (labels, affinity terms) compiled once, as NewPodInfo does at enqueue
     ctx->cluster->pod_table_precompile(p);
+    p.template_id = ctx->engine->intern_template(p);  // the compile memo's key (Engine::compile)
     const int32_t h = ctx->engine->next_handle++;
     ctx->engine->queue[h] = std::move(p);
     *handle = h;
@@ -620,6 +621,20 @@ int ksg_debug_same_pods(const ksg_ctx* ctx, uint64_t* taken, uint64_t* not_taken
   return KSG_OK;
 }
 
+int ksg_debug_same_carry(const ksg_ctx* ctx, uint64_t* loaded, uint64_t* filled) {
+  if (!ctx || !loaded || !filled) return KSG_EINVAL;
+  *loaded = ctx->engine->same_carried_;
+  *filled = ctx->engine->same_filled_;
+  return KSG_OK;
+}
+
+int ksg_debug_compile_memo(const ksg_ctx* ctx, uint64_t* hits, uint64_t* misses) {
+  if (!ctx || !hits || !misses) return KSG_EINVAL;
+  *hits = ctx->engine->memo_hits_;
+  *misses = ctx->engine->memo_misses_;
+  return KSG_OK;
+}
+
 int ksg_debug_sched_same(ksg_ctx* ctx, int32_t handle_a, int32_t handle_b) {
   if (!ctx) return KSG_EINVAL;
   try {
@@ -627,9 +642,10 @@ int ksg_debug_sched_same(ksg_ctx* ctx, int32_t handle_a, int32_t handle_b) {
     auto a = e->queue.find(handle_a), b = e->queue.find(handle_b);
     if (a == e->queue.end() || b == e->queue.end()) return KSG_EINVAL;
     ksg::CompiledPod ca, cb;
-    int rc = e->compile(a->second, ksg::Engine::CYCLE, -1, true, false, &ca);
+    // (compile_full: a question about two programs neither uses nor counts in the compile memo)
+    int rc = e->compile_full(a->second, ksg::Engine::CYCLE, -1, true, false, &ca, nullptr);
     if (rc == KSG_OK) {
-      rc = e->compile(b->second, ksg::Engine::CYCLE, -1, true, false, &cb);
+      rc = e->compile_full(b->second, ksg::Engine::CYCLE, -1, true, false, &cb, nullptr);
       e->c->pod_table_drop(ca.slot);
       if (rc == KSG_OK) e->c->pod_table_drop(cb.slot);
     }

@@ -61,13 +61,17 @@ void Cluster::free_all() {
 
 int32_t Cluster::key_id(const std::string& k) {
   int32_t id = label_keys.get(k);
-  if ((size_t)id >= keys.size()) keys.resize(id + 1);
+  if ((size_t)id >= keys.size()) {
+    keys.resize(id + 1);
+    ++compile_epoch;
+  }
   return id;
 }
 int32_t Cluster::scalar_slot(const std::string& n) {
   int32_t id = scalar_ix.find(n);
   if (id >= 0) return id;
   layout_dirty = true;  // a new column must exist on the device (the layout widens scalar_cols as needed)
+  ++compile_epoch;
   return scalar_ix.get(n);
 }
 uint32_t Cluster::port_id(std::string ip, std::string proto, int32_t port) {  // HostPortInfo.sanitize
@@ -78,6 +82,7 @@ uint32_t Cluster::port_id(std::string ip, std::string proto, int32_t port) {  //
   if (id >= 0) return (uint32_t)id;
   id = port_ix.get(k);
   ports.push_back({ip, proto, port});
+  ++compile_epoch;  // one more bit in every pod's conflict bitmap
   return (uint32_t)id;
 }
 
@@ -141,6 +146,7 @@ const std::vector<std::string>& Cluster::order() {
   if (rebuild) {  // updateNodeInfoSnapshotList(updateAll=true) over nodeTree.list (node_tree.go:119-143)
     ++node_gen_;
     ++list_gen;
+    ++compile_epoch;
     order_.clear();
     size_t longest = 0;
     for (auto& z : zones_) longest = std::max(longest, tree_[z].size());
@@ -186,16 +192,19 @@ bool Cluster::key_unique(int32_t key) {
 // ---- cache events -------------------------------------------------------------------------------
 int Cluster::upsert_namespace(const NamespaceSpec& ns) {
   namespaces[ns.name] = ns;
+  ++compile_epoch;
   return KSG_OK;
 }
 
 // ---- the selecting objects of PodTopologySpread's default constraints ---------------------------
 int Cluster::upsert_object(SelectorObj&& o) {
+  ++compile_epoch;
   if (o.kind == OBJ_SERVICE) services[o.ns][o.name] = std::move(o.sel);
   else owners[o.kind - 1][{o.ns, o.name}] = std::move(o.sel);
   return KSG_OK;
 }
 int Cluster::remove_object(int kind, const std::string& ns, const std::string& name) {
+  ++compile_epoch;
   if (kind == OBJ_SERVICE) {
     auto it = services.find(ns);
     if (it == services.end() || !it->second.erase(name)) return KSG_ENOTFOUND;
@@ -346,6 +355,7 @@ void Cluster::set_node(NodeRec& r, NodeSpec&& n) {  // addNodeImageStates + Node
 // look in other zones), which the informer never asks for.
 int Cluster::add_node(NodeSpec&& n) {
   ++node_gen_;
+  ++compile_epoch;  // taints, images, labels, allocatable bound, the node list
   auto it = nodes_.find(n.name);
   if (it != nodes_.end() && it->second->real) return update_node(std::move(n));
   ++events;
@@ -372,6 +382,7 @@ int Cluster::add_node(NodeSpec&& n) {
 // rewritten in place whenever its taint / image CSR ranges keep their sizes.
 int Cluster::update_node(NodeSpec&& n) {
   ++node_gen_;
+  ++compile_epoch;  // taints, images, labels, allocatable bound, the node list
   auto it = nodes_.find(n.name);
   if (it == nodes_.end() || !it->second->real) return add_node(std::move(n));
   ++events;
@@ -397,6 +408,7 @@ int Cluster::update_node(NodeSpec&& n) {
 // still be on the way), skipped by snapshots and by the pod table's aggregation.
 int Cluster::remove_node(const std::string& name) {
   ++node_gen_;
+  ++compile_epoch;  // taints, images, labels, allocatable bound, the node list
   auto it = nodes_.find(name);
   if (it == nodes_.end() || !it->second->real) { err = "node " + name + " is not found"; return KSG_ENOTFOUND; }
   ++events;
@@ -444,6 +456,9 @@ int Cluster::add_pod(const PodSpec& p, const std::string& uid_override, bool dev
   if (node_name.empty()) { err = "pod is not bound"; return KSG_EINVAL; }
   if (pods.count(uid)) { err = "pod " + uid + " exists"; return KSG_EEXIST; }
   ++events;
+  // (an assume from Engine::run_batch's settle changes nothing a compile reads but what port_id, scalar_slot and
+  // pod_table_put bump for themselves; an informer's pod is rare enough to always count)
+  if (uid_override.empty()) ++compile_epoch;
   NodeRec* r = node(node_name);
   if (!r) {
     auto rec = std::make_unique<NodeRec>();
@@ -492,6 +507,7 @@ int Cluster::remove_pod(const std::string& uid) {
   auto it = pods.find(uid);
   if (it == pods.end()) { err = "unknown pod " + uid; return KSG_ENOTFOUND; }
   ++events;
+  ++compile_epoch;
   NodeRec* r = node(it->second.node);
   pods_with_affinity -= it->second.with_affinity ? 1 : 0;
   req_anti_pods -= it->second.req_anti ? 1 : 0;

@@ -238,8 +238,105 @@ struct SelBuilder {
 static bool empty_term(const NSTerm& t) { return t.exprs.empty() && t.fields.empty(); }
 
 // ---- compile ---------------------------------------------------------------------------------------
+int32_t Engine::intern_template(const PodSpec& p) {
+  std::string key;
+  pod_template_key(p, &key);
+  auto it = templates_.find(key);  // (the bytes are the map's key: equal ids <=> equal bytes, no hash trusted)
+  if (it != templates_.end()) return it->second;
+  const int32_t id = (int32_t)templates_.size();
+  templates_.emplace(std::move(key), id);
+  return id;
+}
+
+// A compiled pod the memo may hold: nothing in it depends on the pod beyond its template, its slot and rot_start --
+// no pod-table aggregation, no node subset or list, no nomination (its own, or the pod's record in the nominee
+// table), no OpportunisticBatching cycle fields, no own affinity terms, no error.
+static bool memo_node_local(const CompiledPod& cp, const PodSpec& p) {
+  if (cp.blob.size() < sizeof(PodDesc) || cp.error || cp.prefilter_reject || cp.prefilter_error || cp.ipa_parse_error ||
+      cp.topo_score_error || cp.sig >= 0)
+    return false;
+  PodDesc d;
+  std::memcpy(&d, cp.blob.data(), sizeof(PodDesc));
+  constexpr uint32_t never = DF_AGGREGATE | DF_SUBSET | DF_NOMINATED | DF_NOM_TOPO | DF_OB | DF_PREFILTER_REJECT |
+                             DF_SCORE_ERROR | DF_EVAL_OUT | DF_NODE_LIST;
+  return !(d.flags & never) && d.n_own_terms == 0 && d.nom_self == -1 && p.nominated_node.empty() && p.node_name.empty();
+}
+
+// the first difference between a memo hit and the full compile of the same pod ("verify"), "" when there is none
+static std::string memo_diff(const CompiledPod& a, const CompiledPod& b) {
+  if (a.blob.size() != b.blob.size())
+    return "program sizes " + std::to_string(a.blob.size()) + " and " + std::to_string(b.blob.size());
+  for (size_t i = 0; i < a.blob.size(); ++i)
+    if (a.blob[i] != b.blob[i]) return "program offset " + std::to_string(i);
+  const bool res = a.res.cpu == b.res.cpu && a.res.mem == b.res.mem && a.res.eph == b.res.eph && a.res.scalar == b.res.scalar &&
+                   a.res.nz_cpu == b.res.nz_cpu && a.res.nz_mem == b.res.nz_mem;
+  if (!res) return "field res";
+  if (a.port_ids != b.port_ids) return "field port_ids";
+#define KSG_MEMO_F(f) \
+  if (a.f != b.f) return "field " #f;
+  KSG_MEMO_F(num_all) KSG_MEMO_F(subset_first) KSG_MEMO_F(prefilter_reject) KSG_MEMO_F(prefilter_code)
+  KSG_MEMO_F(prefilter_plugin) KSG_MEMO_F(error) KSG_MEMO_F(score_mask) KSG_MEMO_F(slot) KSG_MEMO_F(prefilter_error)
+  KSG_MEMO_F(ipa_own_req) KSG_MEMO_F(ipa_parse_error) KSG_MEMO_F(topo_score_error) KSG_MEMO_F(arena_words)
+  KSG_MEMO_F(agg_ok) KSG_MEMO_F(own_terms) KSG_MEMO_F(sig)
+#undef KSG_MEMO_F
+  return "";
+}
+
 int Engine::compile(const PodSpec& p, Mode mode, int plugin, bool assume, bool eval, CompiledPod* out,
                     const uint8_t* node_list) {
+  const int memo = c->cfg.compile_memo;
+  // (a nominee table in use: a pod's own record and its mark are per pod; OpportunisticBatching: per-cycle fields)
+  if (memo == 0 || mode != CYCLE) return compile_full(p, mode, plugin, assume, eval, out, node_list);
+  if (p.template_id < 0 || nom_active_ || ob_acting()) {
+    ++memo_misses_;
+    return compile_full(p, mode, plugin, assume, eval, out, node_list);
+  }
+  (void)c->order();  // a pending rebuild of the snapshot's node list moves the epoch (compile_full starts with it too)
+  const bool rd = rotdev();
+  if (memo_.valid && memo_.tid == p.template_id && memo_.assume == assume && memo_.eval == eval && memo_.rotdev == rd &&
+      memo_.epoch == c->compile_epoch) {
+    *out = memo_.cp;
+    PodDesc& D = *reinterpret_cast<PodDesc*>(out->blob.data());
+    const int32_t N = out->num_all;  // (no subset: the whole snapshot)
+    D.rot_start = N ? (int32_t)(c->next_start % N) : 0;
+    if (assume) {
+      D.slot = next_slot_ >= 0 ? next_slot_ : c->pod_table_put(p, -1);
+      out->slot = D.slot;
+    }
+    ++memo_hits_;
+    if (memo == 2) {  // the full compile into the same slot (nothing is reserved twice), compared field by field
+      CompiledPod full;
+      const int32_t keep = next_slot_;
+      next_slot_ = out->slot;
+      const int rc = compile_full(p, mode, plugin, assume, eval, &full, node_list);
+      next_slot_ = keep;
+      const std::string diff = rc ? std::string() : memo_diff(*out, full);
+      if (rc || !diff.empty()) {
+        if (assume && keep < 0) c->pod_table_drop(out->slot);  // taken above; the caller releases only compiled pods'
+        if (rc) return rc;
+        c->err = "compileMemo verify: pod " + p.ns + "/" + p.name + " differs from its full compile at " + diff;
+        return KSG_EINVAL;
+      }
+    }
+    return KSG_OK;
+  }
+  ++memo_misses_;
+  const int rc = compile_full(p, mode, plugin, assume, eval, out, node_list);
+  if (rc) return rc;
+  if (memo_node_local(*out, p)) {
+    memo_.valid = true;
+    memo_.tid = p.template_id;
+    memo_.assume = assume;
+    memo_.eval = eval;
+    memo_.rotdev = rd;
+    memo_.epoch = c->compile_epoch;  // as the compile left it: what it interned itself is in the entry
+    memo_.cp = *out;
+  }
+  return KSG_OK;
+}
+
+int Engine::compile_full(const PodSpec& p, Mode mode, int plugin, bool assume, bool eval, CompiledPod* out,
+                         const uint8_t* node_list) {
   const Config& cfg = c->cfg;
   using pclk = std::chrono::steady_clock;
   pclk::time_point pt = cfg.loop_stamps ? pclk::now() : pclk::time_point{};
@@ -1327,7 +1424,7 @@ Engine::~Engine() {
   for (DevBuf* b : {&d_descs, &d_meta, &d_status, &d_fmask, &d_blk, &d_fixed, &d_raw, &d_out,
                     &d_total, &d_arena, &d_xa, &d_xp, &d_xb, &d_xs, &d_gran, &d_fail, &d_grp, &d_agran, &d_region, &d_astamps, &d_aspill, &d_relay,
                     &d_evg, &d_aggpeers, &d_pre, &d_seg, &d_segcnt, &d_psout, &d_pdb, &d_pick, &d_contrib_buf, &d_wide, &d_vsc,
-                    &d_ob, &d_ob_heap, &d_ob_map, &d_tcache, &d_tcw, &d_nom, &d_diag, &d_diag_sum, &d_xn})
+                    &d_ob, &d_ob_heap, &d_ob_map, &d_tcache, &d_tcw, &d_nom, &d_diag, &d_diag_sum, &d_xn, &d_carry})
     if (b->p) (void)hipFree(b->p);
   if (h_pinned) (void)hipHostFree(h_pinned);
   if (h_tcw) (void)hipHostFree(h_tcw);
@@ -2627,6 +2724,10 @@ int Engine::run_batch(const std::vector<const PodSpec*>& pods, const std::vector
     }
     return KSG_OK;
   };
+  // The carry (config loopSameCarry): the last kernel enqueued that wrote node columns, when it was a k_sched_same
+  // run of this batch -- its first pod, its instance and its tag.  Anything else that touches the mirror (another
+  // kernel, a drain with ensure_mirror) forgets it; k_same_diag only reads.  Nothing is carried between batches.
+  struct CarryPrev { bool valid; int first; bool sampled; uint32_t tag; } carry_prev{false, 0, false, 0u};
   // compile + stage the chunk starting at pod i while the device runs the chunks before it
   auto next_chunk = [&](int i) -> int {
     const int b = chunk_end(i);
@@ -2663,6 +2764,7 @@ int Engine::run_batch(const std::vector<const PodSpec*>& pods, const std::vector
       // the mirror must be re-laid out or the buffers grown: drain the device and mirror what it
       // assumed first (the same state a batch boundary here would give)
       htrace("drain", i);
+      carry_prev.valid = false;  // the mirror is about to be touched
       if ((r2 = drain())) return r2;
       if (c->cfg.loop_stamps)
         std::fprintf(stderr, "[host] pipeline drained before pod %d (%s)\n", i,
@@ -2691,6 +2793,11 @@ int Engine::run_batch(const std::vector<const PodSpec*>& pods, const std::vector
   const bool same_ok = use_loop && c->cfg.loop_same_template && W == 1 && !comm && m.nom == nullptr &&
                        (!diag || c->cfg.loop_same_diag) && !c->cfg.loop_stamps && c->cfg.debug_give_up_at < 0 &&
                        m.n <= kSameMaxNodes;
+  if (same_ok && c->cfg.loop_same_carry) {
+    const bool fresh = d_carry.p == nullptr;
+    if ((rc = ensure(d_carry, (size_t)kSameCarryWords * 8))) return rc;
+    if (fresh) HIPCHK(hipMemsetAsync(d_carry.p, 0, (size_t)kSameCarryWords * 8, s));
+  }
   int ss_at = -1, ss_len = 0;  // the last stretch measured
   // pods [a, a + result) are eligible and of one template (within the chunk and a launch's pod limit)
   auto same_stretch = [&](int a, int cut) -> int {
@@ -2762,6 +2869,7 @@ int Engine::run_batch(const std::vector<const PodSpec*>& pods, const std::vector
       htrace("loop", i);
       hipEvent_t t0 = tl ? lev[2 * runs.size()] : nullptr, t1 = tl ? lev[2 * runs.size() + 1] : nullptr;
       if (comm && comm->in_process()) {
+        carry_prev.valid = false;
         GroupReq req{};
         req.la = LoopGroupArg{m, bv, lv};
         req.t0 = t0;
@@ -2769,11 +2877,21 @@ int Engine::run_batch(const std::vector<const PodSpec*>& pods, const std::vector
         if ((rc = group_launch(&req, false, GS, unit))) return rc;
       } else if (same_run) {
         // (rotdev() is per batch: the run's pods all carry DF_ROTDEV, or none does)
-        HIPCHK(launch_sched_same(m, bv, lv, s, t0, t1,
-                                 (reinterpret_cast<const PodDesc*>(cp[i].blob.data())->flags & DF_ROTDEV) != 0));
+        const bool samp = (reinterpret_cast<const PodDesc*>(cp[i].blob.data())->flags & DF_ROTDEV) != 0;
+        if (c->cfg.loop_same_carry) {
+          lv.carry = (unsigned long long*)d_carry.p;
+          if (++carry_seq_ == 0u) ++carry_seq_;
+          lv.carry_tag = carry_seq_;
+          const bool load = carry_prev.valid && carry_prev.sampled == samp && same_programs(cp[carry_prev.first], cp[i]);
+          lv.carry_expect = load ? carry_prev.tag : 0u;
+          ++(load ? same_carried_ : same_filled_);
+          carry_prev = CarryPrev{true, i, samp, lv.carry_tag};
+        }
+        HIPCHK(launch_sched_same(m, bv, lv, s, t0, t1, samp));
         // the run's FitErrors: a suffix of it, reduced once from the mirror as the run leaves it
         if (diag) HIPCHK(launch_same_diag(m, bv, i, j - i, (int32_t*)d_diag.p, s));
       } else {
+        carry_prev.valid = false;
         HIPCHK(launch_sched_loop(m, bv, lv, s, t0, t1, unit));
       }
       runs.push_back({i, j - i, rb, false, tl});
@@ -2782,6 +2900,7 @@ int Engine::run_batch(const std::vector<const PodSpec*>& pods, const std::vector
       continue;
     }
     if (use_agg && agg_loop_ok(cp[i])) {  // a run of pod-table pods: one k_agg_loop launch
+      carry_prev.valid = false;
       int j = i;
       double rb = 0;
       int32_t gw = 1;
@@ -2879,6 +2998,7 @@ int Engine::run_batch(const std::vector<const PodSpec*>& pods, const std::vector
       i = j;
       continue;
     }
+    carry_prev.valid = false;  // the launch path
     if (comm) {  // sharded, not loop-eligible: the per-pod RCCL exchange path
       if ((rc = run_sharded(cp, bv, i, i + 1, &launches, &bytes, &timed))) return rc;
       ++i;

@@ -151,8 +151,13 @@ struct PodSpec {
   // NodeDeclaredFeatures' PreFilter would not Skip: the pod needs a declared node feature
   // (component-helpers/nodedeclaredfeatures: RestartAllContainers rules, hostNetwork with hostUsers false)
   bool needs_features = false;
+  // The pod's template, interned per context at ksg_pod_compile (same context only, as pt_pre): two pods of a
+  // context have the same id iff every field above other than name and uid is equal (pod_template_key's bytes are
+  // compared, not a hash of them).  -1: not interned (a pod that did not come through ksg_pod_compile).
+  int32_t template_id = -1;
 };
 bool pod_scalar_free(const PodSpec& p);  // the check behind PodSpec::scalar_free
+void pod_template_key(const PodSpec& p, std::string* out);  // PodSpec::template_id's canonical bytes
 struct NodeImage { std::vector<std::string> names; int64_t size; };
 struct NodeSpec {
   std::string name;
@@ -260,7 +265,15 @@ struct Config {
   // k_same_diag behind each ("loopSameDiag"), and sampled pods in k_agg_loop's diagnosing sampling instances
   // ("aggLoopSampledDiag"); false: such a batch is routed as before (k_sched_loop / the launch path)
   bool loop_same_diag = true;
+  // k_sched_same: a launch ends by writing its cached state to the engine's carry buffer and the next launch of the
+  // batch, when it runs the same program on the same instance with nothing in between, loads it instead of evaluating
+  // its fill ("loopSameCarry"; false, the default: every launch fills, as before -- the kernel time falls by 0.12 us
+  // per pod at C2 but not every bench run was faster, profiles/same_carry_bench_ab.txt)
+  bool loop_same_carry = false;
   bool agg_loop_sampled_diag = true;
+  // Engine::compile's memo of the last node-local program ("compileMemo": "on" 1, "off" 0, "verify" 2 -- every hit is
+  // also compiled in full and compared, the call fails on a difference)
+  int compile_memo = 1;
   bool resident_ahead = true;  // resident loops: the next pod's phase 1 ahead of its doorbell (LoopView, AggView bit 7)
   int debug_give_up_at = -1;    // diagnostic: the persistent loops give up at this pod of a run
   int loop_wg = 0;              // k_sched_loop workgroups (0: min(node units, CUs, 128))
@@ -496,6 +509,10 @@ class Cluster {
   // ksg_generation: cache mutations applied (node add / update / remove, pod add / remove -- assumes and
   // forgets included) and rebuilds of the snapshot's node list (its order may have changed)
   uint64_t events = 0, list_gen = 0;
+  // Engine::compile's memo: bumped by every change to what a pod's compile reads beyond the pod -- the node list,
+  // taints, host-port ids, scalar slots, label keys, image states, alloc_bound, the existing-pod key tables,
+  // namespaces, services and owners.  Not by an assume of a pod without ports, scalars or terms.
+  uint64_t compile_epoch = 0;
   double taint_ids_per_node = 0, img_ids_per_node = 0;  // CSR densities (algorithmic-bytes model)
   int64_t taint_max_per_node = 0;                        // bounds k_sched_loop's raw-score granules
   int64_t alloc_bound = 0;                               // max cpu/memory allocatable seen (INT64_MAX: a negative one)
@@ -616,6 +633,20 @@ class Engine {
   // compile `p` for the current cluster; rot_start from Cluster::next_start
   int compile(const PodSpec& p, Mode mode, int plugin, bool assume, bool eval, CompiledPod* out,
               const uint8_t* node_list = nullptr);
+  // The compile memo (config compileMemo): compile() keeps the last node-local CompiledPod a CYCLE-mode
+  // compile_full produced; a later call for a pod of the same template (PodSpec::template_id), with the same assume /
+  // eval / rotdev() and an unchanged Cluster::compile_epoch, copies it and sets the pod's slot and rot_start.
+  int compile_full(const PodSpec& p, Mode mode, int plugin, bool assume, bool eval, CompiledPod* out,
+                   const uint8_t* node_list);
+  int32_t intern_template(const PodSpec& p);  // PodSpec::template_id: pod_template_key's bytes, interned
+  std::unordered_map<std::string, int32_t> templates_;
+  struct Memo {
+    bool valid = false, assume = false, eval = false, rotdev = false;
+    int32_t tid = -1;
+    uint64_t epoch = 0;
+    CompiledPod cp;
+  } memo_;
+  uint64_t memo_hits_ = 0, memo_misses_ = 0;  // CYCLE-mode compiles served from memo_ / compiled in full (ksg_debug_compile_memo)
   double cprof_[8] = {};  // loopStamps: compile time per section (us), reported with the host line
   std::chrono::steady_clock::time_point api_t0_{};  // loopStamps: ksg_schedule_batch entry
   double reserve_us_ = 0;
@@ -648,6 +679,10 @@ class Engine {
   }
   // pods of k_sched_loop's runs that k_sched_same ran, and that k_sched_loop ran (ksg_debug_same_pods)
   uint64_t same_pods_ = 0, not_same_pods_ = 0;
+  // k_sched_same launches whose fill the host told to load the previous launch's carried state, and the others
+  // (ksg_debug_same_carry; the device loads unless the previous launch gave up, which fails the batch)
+  uint64_t same_carried_ = 0, same_filled_ = 0;
+  uint32_t carry_seq_ = 0;  // LoopView::carry_tag of the last k_sched_same launch (never 0, never repeated in a batch)
   // a pod k_sched_same can take, and whether pod b may follow pod a in one of its runs (engine.cpp)
   // (sampled: config loop_same_sampled -- pods with a device-resident nextStartNodeIndex too; diag: config
   // loop_same_diag -- pods of a diagnosed batch too)
@@ -730,6 +765,7 @@ class Engine {
   DevBuf d_xa, d_xp, d_xb, d_xs;  // node-sharded exchange vectors, one set per pod of the batch
   DevBuf d_xn;                    // ... the own-nomination vector (XnWord; distributed.nominations)
   DevBuf d_evg;             // node-sharded evaluation output, gathered over the ranks
+  DevBuf d_carry;                   // k_sched_same: LoopView::carry (kSameCarryWords words)
   DevBuf d_gran, d_fail, d_stamps;  // k_sched_loop: exchange granules (local), give-up flag, stamps
   uint64_t assume_seq_ = 0;  // assumed pods' cache uids: "<uid>#a<n>", n counted per context
   DevBuf d_grp;  // in-process groups, the leader's: every rank's loop launch arguments (group_launch)

@@ -260,6 +260,69 @@ bool pod_scalar_free(const PodSpec& p) {
     if (!ok(k.req) || !ok(k.st_req) || !ok(k.st_alloc)) return false;
   return ok(p.pod_requests) && ok(p.overhead) && ok(p.pod_st_req) && ok(p.pod_st_alloc);
 }
+
+// PodSpec::template_id's canonical bytes: every field but name and uid (and the per-context pt_pre), each string
+// and list behind its length, so that two pods' bytes are equal iff those fields are.  A field added to PodSpec
+// goes in here too (tests/test_gpu_compile_memo.py's verify mode catches one that compile reads and this misses).
+void pod_template_key(const PodSpec& p, std::string* out) {
+  std::string& o = *out;
+  o.clear();
+  auto raw = [&](const void* v, size_t n) { o.append(static_cast<const char*>(v), n); };
+  auto i64 = [&](int64_t v) { raw(&v, 8); };
+  auto str = [&](const std::string& s) { i64((int64_t)s.size()); o += s; };
+  auto strs = [&](const std::vector<std::string>& v) { i64((int64_t)v.size()); for (auto& s : v) str(s); };
+  auto smap = [&](const StrMap& m) { i64((int64_t)m.size()); for (auto& kv : m) { str(kv.first); str(kv.second); } };
+  auto exprs = [&](const std::vector<Expr>& v) {
+    i64((int64_t)v.size());
+    for (auto& e : v) { str(e.key); str(e.op); strs(e.values); }
+  };
+  auto nsterm = [&](const NSTerm& t) { exprs(t.exprs); exprs(t.fields); };
+  auto lsel = [&](const LabelSel& s) { i64(s.present); smap(s.match); exprs(s.exprs); };
+  auto paterms = [&](const std::vector<PATerm>& v) {
+    i64((int64_t)v.size());
+    for (auto& t : v) { lsel(t.sel); strs(t.namespaces); lsel(t.ns_sel); str(t.topo); i64(t.weight); }
+  };
+  auto resvec = [&](const ResVec& v) {
+    i64((int64_t)v.size());
+    for (auto& r : v) { str(r.name); raw(&r.milli, sizeof r.milli); }
+  };
+  auto conts = [&](const std::vector<Container>& v) {
+    i64((int64_t)v.size());
+    for (auto& k : v) {
+      str(k.name); str(k.image); resvec(k.req);
+      i64((int64_t)k.ports.size());
+      for (auto& hp : k.ports) { str(hp.ip); str(hp.proto); i64(hp.port); }
+      i64(k.sidecar); i64(k.has_status); resvec(k.st_req); resvec(k.st_alloc);
+    }
+  };
+  str(p.ns); smap(p.labels); i64(p.terminating); str(p.node_name);
+  i64(p.has_node_selector); smap(p.node_selector);
+  i64(p.has_required_na); i64((int64_t)p.required_na.size());
+  for (auto& t : p.required_na) nsterm(t);
+  i64(p.has_preferred_na); i64((int64_t)p.preferred_na.size());
+  for (auto& t : p.preferred_na) { i64(t.first); nsterm(t.second); }
+  i64(p.has_pod_affinity); i64(p.has_pod_anti);
+  paterms(p.aff_req); paterms(p.anti_req); paterms(p.aff_pref); paterms(p.anti_pref);
+  i64((int64_t)p.tolerations.size());
+  for (auto& t : p.tolerations) { str(t.key); str(t.op); str(t.value); str(t.effect); }
+  conts(p.containers); conts(p.init_containers);
+  i64(p.has_overhead); resvec(p.overhead); resvec(p.pod_requests);
+  i64(p.has_pod_status_res); resvec(p.pod_st_req); resvec(p.pod_st_alloc);
+  i64(p.resize_infeasible); i64(p.has_status_res);
+  i64((int64_t)p.spreads.size());
+  for (auto& s : p.spreads) {
+    i64(s.max_skew); str(s.key); str(s.when); lsel(s.sel); i64(s.min_domains); i64(s.aff_honor); i64(s.taint_honor);
+    strs(s.match_label_keys);
+  }
+  strs(p.image_volumes); str(p.unsupported);
+  i64(p.has_controller); str(p.owner_api); str(p.owner_kind); str(p.owner_name);
+  i64(p.priority); i64(p.has_start); i64(p.start_ns); i64(p.preempt_never); str(p.nominated_node);
+  i64(p.preempt_terminating); i64(p.scalar_free);
+  for (const std::string* s : {&p.sign.sched, &p.sign.tols, &p.sign.labels, &p.sign.ports, &p.sign.na, &p.sign.nsel,
+                               &p.sign.images, &p.sign.vols})
+    str(*s);
+  i64(p.sign.claims); i64(p.needs_features);
+}
 static void pod_sign_fragments(const JDoc& d, const JVal& root, PodSpec* out);  // below
 
 bool decode_pod(const char* p, size_t n, PodSpec* out, std::string* err) {
@@ -929,8 +992,17 @@ bool decode_config(const char* p, size_t n, Config* c, std::string* err) {
     if (const JVal* as = d.get(r, "aggLoopSampled")) c->agg_loop_sampled = !(as->type == JVal::BOOL && !as->b);
     if (const JVal* rs = d.get(r, "residentAggSampled")) c->resident_agg_sampled = !(rs->type == JVal::BOOL && !rs->b);
     if (const JVal* sd = d.get(r, "loopSameDiag")) c->loop_same_diag = !(sd->type == JVal::BOOL && !sd->b);
+    if (const JVal* sc = d.get(r, "loopSameCarry")) c->loop_same_carry = sc->type == JVal::BOOL && sc->b;
     if (const JVal* ad = d.get(r, "aggLoopSampledDiag")) c->agg_loop_sampled_diag = !(ad->type == JVal::BOOL && !ad->b);
     if (const JVal* ra = d.get(r, "residentAhead")) c->resident_ahead = !(ra->type == JVal::BOOL && !ra->b);
+    if (d.present(r, "compileMemo")) {  // Engine::compile's one-entry memo
+      const std::string cm = d.str(r, "compileMemo");
+      if (cm != "on" && cm != "off" && cm != "verify") {
+        *err = "compileMemo: Unsupported value \"" + cm + "\" (\"on\", \"off\" or \"verify\")";
+        return false;
+      }
+      c->compile_memo = cm == "off" ? 0 : cm == "on" ? 1 : 2;
+    }
     c->first_chunk = std::max(8, std::min(256, (int)d.num(r, "pipelineFirstChunk", 32)));
     if (c->loop_wave_map < 0 || c->loop_wave_map > 2) c->loop_wave_map = 0;
     if (const JVal* dx = d.get(r, "deviceExchange")) c->dev_exchange = dx->type == JVal::BOOL && dx->b ? 1 : 0;

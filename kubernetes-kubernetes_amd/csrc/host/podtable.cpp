@@ -165,6 +165,7 @@ int32_t Cluster::pod_table_put(const PodSpec& p, int32_t node_index) {
     pt_terms[s].push_back(j);
     auto& m = t.kind == T_REQ_ANTI ? exanti_keys : t.kind == T_REQ_AFF ? score_keys_req : score_keys_pref;
     m[d.key]++;
+    ++compile_epoch;  // the existing-pod key tables
   }
   pods_dirty = true;
   return s;
@@ -229,6 +230,7 @@ void Cluster::pod_table_drop(int32_t s) {
     auto& m = d.kind == T_REQ_ANTI ? exanti_keys : d.kind == T_REQ_AFF ? score_keys_req : score_keys_pref;
     auto it = m.find(d.key);
     if (it != m.end() && --it->second <= 0) m.erase(it);
+    ++compile_epoch;
     d.kind = T_DEAD;
     d.owner = -1;
     tt_free.push_back(j);

@@ -140,6 +140,26 @@ class Scheduler(Backend):
         self._chk(fn(self.ctx, C.byref(a), C.byref(b)), "lean_pods")
         return a.value, b.value
 
+    def compile_memo(self):
+        """(hits, misses): the scheduling cycles' host compiles so far that copied the compile memo's program, and
+        that compiled in full (ksg_debug_compile_memo; bound on first use, as lean_pods)."""
+        fn = self.lib.ksg_debug_compile_memo
+        fn.restype = C.c_int
+        fn.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+        a, b = C.c_uint64(), C.c_uint64()
+        self._chk(fn(self.ctx, C.byref(a), C.byref(b)), "compile_memo")
+        return a.value, b.value
+
+    def same_carry(self):
+        """(loaded, filled): the k_sched_same launches so far that loaded the previous launch's carried state, and
+        that evaluated their fill (ksg_debug_same_carry; bound on first use, as lean_pods)."""
+        fn = self.lib.ksg_debug_same_carry
+        fn.restype = C.c_int
+        fn.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+        a, b = C.c_uint64(), C.c_uint64()
+        self._chk(fn(self.ctx, C.byref(a), C.byref(b)), "same_carry")
+        return a.value, b.value
+
     def same_pods(self):
         """(taken, not_taken): the pods of k_sched_loop's runs so far that k_sched_same ran, and that k_sched_loop
         ran (ksg_debug_same_pods; bound on first use, as lean_pods)."""
